@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- DynamicEmb lookup+pool forward/backward on MI355X (BASELINE.json configs[1], "C2").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step = one pass of the hot path over one synthetic batch that is already resident in HBM:
 forward (dedup -> hash lookup -> [insert + init of unseen keys: none in steady state] -> fused
@@ -14,7 +14,9 @@ a fixed permutation (seed 1234); every timed batch is different; all touched key
 (steady state).  N > 1: row-wise model-parallel shards, one process per GPU, keys all-to-all out /
 pooled partial sums back; weak scaling (per-GPU batch fixed).
 
-Prints ONE JSON line (rank 0).  `value` = lookups (keys) per second of the whole job.
+Prints ONE JSON line (rank 0).  `value` = lookups (keys) per second of the whole job; `ms_per_step` = one of the K timed steps.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (see `dump_outputs`); the inputs depend on the
+arguments only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -57,7 +59,12 @@ def parse():
     ap.add_argument("--shard-mode", default="auto", choices=["auto", "rows", "partial"])
     ap.add_argument("--capacity-factor", type=float, default=0.0,
                     help="sharded path: fixed-capacity key exchange with this factor (0: exact all-to-all-v with one host read)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def zipf_keys(min_val, max_val, exponent, size, device):
@@ -683,6 +690,47 @@ def sharded_stage_times(sharded, batches, grad, dist, device, world, step_ms):
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def _seeded_subset(n, cap, seed):
+    """None when all n items fit under `cap`; else `cap` indices in [0, n), drawn by a fixed seed and sorted"""
+    if n <= cap:
+        return None
+    g = torch.Generator().manual_seed(seed)
+    return torch.randperm(n, generator=g)[:cap].sort().values
+
+
+def dump_outputs(dirname, out, keys, module):
+    """`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy (at most DUMP_BUDGET_BYTES in all):
+      pooled.npy       the step's pooled forward output [B, D] (bf16 held exactly in float32) -- what module(keys, offsets)
+                       returned; above 48 MB a seeded sample of its bags, whose indices are in pooled_bags.npy (float64)
+      rows.npy         unsharded path: the table rows [n, D] fp32 of a seeded sample of up to 16384 of the step's distinct
+                       keys, read after the step's SGD update (a CONST lookup: scores stay put); their keys in rows_keys.npy
+    The hot rows' gradients are summed with float atomics, so the rows, and the pooled sums later steps read from them, may
+    differ in the last bits from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    pooled = out.detach().float()
+    B, D = pooled.shape
+    bags = _seeded_subset(B, max(1, 48_000_000 // (4 * D)), seed=101)
+    if bags is not None:
+        pooled = pooled[bags.to(pooled.device)]
+        arrays["pooled_bags"] = bags.double().numpy()
+    arrays["pooled"] = pooled.cpu().numpy()
+    if module is not None:
+        uk = torch.unique(keys).cpu()
+        pick = _seeded_subset(uk.numel(), min(16384, 12_000_000 // (4 * D + 8)), seed=102)
+        sample = uk if pick is None else uk[pick]
+        found, rows = module.lookup_rows(sample.to(keys.device))
+        assert bool(found.all()), "a key of the last timed step is missing from the table"
+        arrays["rows"] = rows.float().cpu().numpy()
+        arrays["rows_keys"] = sample.double().numpy()       # keys < rows <= 2^53: exact
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _flush_c_stdout():
     try:
         import ctypes
@@ -767,7 +815,9 @@ def main():
         def bwd(st, grad):
             sharded.backward(st, grad)
 
-    grad = (torch.randn(args.batch, args.dim, device=device) * 0.01).to(torch.bfloat16)
+    g_grad = torch.Generator(device=device)
+    g_grad.manual_seed(4242 + rank)
+    grad = (torch.randn(args.batch, args.dim, device=device, generator=g_grad) * 0.01).to(torch.bfloat16)
 
     # steady state: every key of every batch is already in the table
     with torch.no_grad():
@@ -794,12 +844,16 @@ def main():
         _flush_c_stdout()   # every rank: RCCL's banner (NCCL_DEBUG=VERSION on the box) leaves the C buffer now, not at exit
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.warmup, n_batches):
+    for i in range(args.warmup, n_batches - 1):
         step(i)
+    last_out, _ = step(n_batches - 1)
     torch.cuda.synchronize()
     if sharded_path:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before anything else runs a step on the table
+        dump_outputs(args.dump_outputs, last_out, batches[n_batches - 1][0], None if sharded_path else module)
+    del last_out
     keys_local = sum(batches[i][0].numel() for i in range(args.warmup, n_batches))
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
