@@ -822,6 +822,45 @@ int mi355_hstu_attn_bwd_rab_f16(const void* dout, const void* q, const void* k, 
                             int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream);
 
 
+/* ---- HSTU attention on FP8 (OCP e4m3fn) operands (csrc/hstu_fp8.hip) ----
+ * Quantisers of hopper/hstu_attn_interface.py:32-292 (quantize_for_two_directions, quantize_for_block_scale,
+ * quantize_for_head_batch_tensor), bit for bit: x [total, num_heads, head_dim] bf16 (x_is_f16 = 0) or fp16, contiguous;
+ * out_fp8 the same shape in e4m3fn bytes.  kind:
+ *   0  x.to(float8_e4m3fn) (quant_mode 0; no descale)
+ *   1  per (token, head) (quant_mode 1, q / k: :40-49): descale[h * descale_stride + t]
+ *   2  per (128-token tile, head, column) (quant_mode 1, vt: :51-117): descale [num tiles, num_heads, head_dim]
+ *   3  per (block_size-token tile, head) (quant_mode 2: :119-192): descale[h * descale_stride + tile]
+ *   4 / 5 / 6  per (sequence, head) / sequence / tensor (quant_mode 3 / 4 / 5: :223-292): descale [B, H] / [B] / [1]
+ * Kinds 2 .. 6 walk the tiles of cu_blocks (mi355_hstu_fp8_cu_blocks with block_size 128, or the mode-2 block size);
+ * num_blocks_bound >= its last entry sizes the grid (mi355_hstu_fp8_blocks_bound).  Kinds 4 .. 6 take amax_work, a zeroed
+ * uint32 array of one entry per descale. */
+int mi355_hstu_fp8_cu_blocks(const int32_t* seq_offsets, int64_t batch, int64_t block_size, int32_t* cu_blocks,
+                             hipStream_t stream);
+int64_t mi355_hstu_fp8_blocks_bound(int64_t total, int64_t batch, int64_t block_size);
+int mi355_hstu_fp8_quantize(int kind, const void* x, int x_is_f16, int64_t total, int64_t num_heads, int64_t head_dim,
+                            const int32_t* seq_offsets, int64_t batch, int64_t block_size, const int32_t* cu_blocks,
+                            int64_t num_blocks_bound, void* out_fp8, float* descale, int64_t descale_stride,
+                            uint32_t* amax_work, hipStream_t stream);
+/* FP8 forward of self-attention (cu_seqlens_q == cu_seqlens_k): the quant_mode 0 .. 5 arms of hstu_hopper_cuda.varlen_fwd
+ * (hopper/hstu_api.cpp:520-566; arithmetic mainloop_fwd_sm90_tma_gmma_ws.hpp:1342-1470).  q / k / v: e4m3fn bytes with
+ * row / head strides in bytes (multiples of 16); in mode 1, v is the reference's vt.  out: fp16, strides in elements.
+ * head_dim 64 / 128 / 256; masks as mi355_hstu_attn_fwd_rab (window_left / window_right, num_contexts / num_targets with the
+ * causal window (-1, 0)).  Descales per mode: 1: descale_q / descale_k [H, >= total] (row stride = descale_*_stride),
+ * descale_v = descale_vt [tiles, H, head_dim] (tile stride = descale_v_stride) with cu_seqlens_descale_vt;
+ * 2: [H, blocks] with cu_seqlens_block_descale_q (128-row blocks) / _kv (block_kv = 64 or 128 keys); 3: [B, H]; 4: [B];
+ * 5: [1]; mode 0 reads none. */
+int mi355_hstu_attn_fwd_fp8(int quant_mode, const void* q, const void* k, const void* v, void* out, int64_t q_row_stride,
+                            int64_t k_row_stride, int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride,
+                            int64_t k_head_stride, int64_t v_head_stride, int64_t o_head_stride, const int32_t* cu_seqlens,
+                            int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                            const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                            int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen,
+                            const float* descale_q, const float* descale_k, const float* descale_v,
+                            int64_t descale_q_stride, int64_t descale_k_stride, int64_t descale_v_stride,
+                            const int32_t* cu_seqlens_descale_vt, const int32_t* cu_seqlens_block_descale_q,
+                            const int32_t* cu_seqlens_block_descale_kv, int64_t block_kv, hipStream_t stream);
+
+
 #ifdef __cplusplus
 }
 #endif

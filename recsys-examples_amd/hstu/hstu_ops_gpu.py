@@ -11,6 +11,7 @@ is read inside the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func); next to a relati
 `window_size_left / right` with a finite side run the local-window kernels, `rab` / `has_drab` the bias kernels."""
 import torch
 
+from .hstu_fp8 import _FP8_TYPES
 from .hstu_attn_interface import (_check_func, func_mask_bias, hstu_varlen_bwd_func, hstu_varlen_fwd_func, hstu_varlen_bwd, hstu_varlen_bwd_rab, hstu_varlen_bwd_window, hstu_varlen_fwd,
                                   hstu_varlen_fwd_rab, hstu_varlen_fwd_window)
 
@@ -36,6 +37,10 @@ def _check(q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, wl, wr, rab,
         raise RuntimeError("rab must be (batch, nheads or 1, max_seqlen_k, max_seqlen_k) with a contiguous last dimension")
     if quant_mode not in (-1, None) or any(e is not None for e in extra):
         raise NotImplementedError("fp8 quantisation is not supported")
+    if any(t.dtype in _FP8_TYPES for t in (q, k, v)):
+        # the FBGEMM source of these ops is absent from the reference (third_party/FBGEMM is empty): their FP8 argument
+        # convention is unknown, so fp8 operands are refused rather than guessed (hstu.varlen_fwd takes the hopper one)
+        raise NotImplementedError("fp8 q / k / v are not supported by the fbgemm raw ops (use hstu.varlen_fwd)")
     if q.dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError("HSTU only supports fp16 and bf16 data type")
     if max_q != max_k or q.shape[0] != k.shape[0] or cu_q.shape != cu_k.shape:

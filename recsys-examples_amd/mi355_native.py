@@ -169,6 +169,13 @@ _SIGS = {
     "mi355_rw_output_pooled": [c_p, c_p, c_p, c_i64, c_int, c_p, c_int, c_p],
     "mi355_rw_allgather": [c_p, c_p, c_p, c_i64, c_p],
     "mi355_rw_alltoallv": [c_p, c_p, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_fp8_cu_blocks": [c_p, c_i64, c_i64, c_p, c_p],
+    "mi355_hstu_fp8_blocks_bound": [c_i64, c_i64, c_i64],
+    "mi355_hstu_fp8_quantize": [c_int, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p,
+                                c_p],
+    "mi355_hstu_attn_fwd_fp8": [c_int, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64,
+                                c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p, c_i64, c_i64,
+                                c_i64, c_p, c_p, c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -194,6 +201,7 @@ _RESTYPES = {
     "mi355_profile_ms": c_f,
     "mi355_demb_aux_numel": c_i64,
     "mi355_demb_forward_fused_workspace_bytes": c_i64,
+    "mi355_hstu_fp8_blocks_bound": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
