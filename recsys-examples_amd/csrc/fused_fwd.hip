@@ -2402,9 +2402,12 @@ int mi355_demb_forward_fused(
   rerun_chain:
     if (rerun) {
       // the chain of the per-slot-counter path over the same buffers, gated on this call's epoch: probe (keys already inserted are
-      // found; Assign / timer scores are idempotent, counting ones see the step twice), numbering, CSR scatter (eager reverse
-      // indices); the pooled output above is complete either way
+      // found), numbering, CSR scatter (eager reverse indices); the pooled output above is complete either way.  The first pass
+      // inserted and scored every key of the step -- only its bookkeeping flooded -- so the re-probe must not count them again:
+      // Assign / timer scores are idempotent, a counting find policy drops its count (LFU scores once per step)
       FusedArgs b = a;
+      if (b.find_policy == kAccumulate) b.find_policy = kConst;
+      else if (b.find_policy == kLruLfu) b.find_policy = kGlobalTimer;
       b.P = 0; b.spp = 1; b.rec = nullptr; b.rec_out = nullptr; b.rec_out4 = nullptr; b.tile_bags = nullptr; b.occ_trank = nullptr;
       b.mt = 0; b.ptab = nullptr; b.rerun_mark = nullptr;
       b.notice = nullptr;
