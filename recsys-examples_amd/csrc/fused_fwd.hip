@@ -82,7 +82,7 @@ struct FusedArgs {
   int64_t batch;                  // bags per feature
   int T;
   int find_policy, insert_policy, use_count;
-  int dbg;                        // MI355_FUSED_DBG (profiling only): 1 skip the slot-counter atomic, 2 skip the probe
+  int dbg;                        // timing-probe bits (the library passes 0; set, results are wrong): 1 skip the slot-counter atomic, 2 skip the probe
   uint64_t score_value, timer;
   InitArgs init;
   // per-step outputs
@@ -249,7 +249,7 @@ __device__ __forceinline__ void wave_init_row(const FusedArgs& a, void* rp, uint
   }
 }
 
-// kFast (opt-in, MI355_FUSED_FASTMOD=1; bucket capacity a power of two): the key's bucket without 64-bit divisions.  gfx950
+// kFast (bucket capacity a power of two; no launch of the library sets it): the key's bucket without 64-bit divisions.  gfx950
 // has no 64-bit divide -- `(hash % (buckets * C)) / C` expands to ~400 instructions per key ahead of the digest load.
 // floor((h mod n C) / C) = floor(h / C) mod n; h / C is a shift, and x mod n = x - mulhi64(x, M) n with M = floor((2^64 - 1) / n)
 // leaves a quotient that is at most one short: two conditional subtractions make it exact.  M is formed once per table and
@@ -2032,17 +2032,11 @@ static inline int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 static inline int part_count(int64_t n, int64_t num_tables) {
   static const int env = getenv("MI355_FUSED_PART") ? atoi(getenv("MI355_FUSED_PART")) : 2;
   // several tables (round 4): path (c) only, with table-aligned partitions -- every table owns at least one, so the batch needs
-  // a few per table (MI355_FUSED_MT=0: multi-table batches keep the per-slot-counter path)
-  constexpr int mt_env = 1;
+  // a few per table
   if (!env || n < (64 << 10)) return 0;
   if (n > (int64_t)kPartMax * 1024) return 0;
-  if (num_tables != 1 && (!mt_env || env < 2 || num_tables < 1 || num_tables > kFusedMaxT)) return 0;
-  // keys per partition (MI355_FUSED_KPP, default 1024): the partition kernel is one block per partition and a chain of dependent
-  // phases -- below 256 partitions it leaves CUs idle, so small batches may as well get thinner partitions
-  constexpr int kpp_env = 1024;
-  const int kpp = kpp_env >= 256 && kpp_env <= 1024 ? kpp_env : 1024;
-  int P = (int)((n + 1023) / 1024);
-  if (kpp < 1024 && P < 256) { P = (int)((n + kpp - 1) / kpp); if (P > 256) P = 256; }
+  if (num_tables != 1 && (env < 2 || num_tables < 1 || num_tables > kFusedMaxT)) return 0;
+  int P = (int)((n + 1023) / 1024);   // 1024 keys per partition
   if (num_tables > 1 && P < 4 * num_tables) return 0;
   // the partition kernel of path (c) is one 1024-thread block per partition and per CU: up to 1.5 K keys per partition (about
   // 1.1 K records of the 2 K a partition can hold) the batch gets exactly one block per CU instead of a second, thin generation
@@ -2107,8 +2101,7 @@ int mi355_demb_forward_fused(
   a.keys = (const uint64_t*)keys; a.n = n; a.offsets = offsets; a.feature_offsets = feature_offsets; a.num_bags = num_bags; a.batch = batch_size;
   a.T = (int)num_tables; a.find_policy = find_policy; a.insert_policy = insert_policy; a.use_count = use_count;
   a.score_value = score_value; a.timer = timer_override;
-  constexpr int dbg_env = 0;
-  a.dbg = dbg_env;
+  a.dbg = 0;
   a.init = InitArgs{init_mode, p0, p1, p2, p3, seed, state_init};
   a.seg_out = (int64_t*)w; w += al256(8 * (num_tables + 1));
   uint64_t* unique_keys = (uint64_t*)w; w += al256(8 * n);
@@ -2162,15 +2155,13 @@ int mi355_demb_forward_fused(
   }
   if (train) MI355_CHECK_ARG(reverse_indices && unique_offsets && slots && row_addr && csr_cnt && csr_rank, "persisted outputs required in train mode");
   // ---- path (c): partition blocks write the CSR and ride in the gather's launch (pooled training forward of one-column-group
-  //      rows with short bags; MI355_FUSED_PART=1 keeps round 2's probe / partition / scatter / gather chain)
+  //      rows with short bags; MI355_FUSED_PART=0 or 1 keeps every batch on the per-slot counters)
   static const int part_env = getenv("MI355_FUSED_PART") ? atoi(getenv("MI355_FUSED_PART")) : 2;
   int lg = 3;
   while ((4 << lg) < emb_dim && lg < 6) ++lg;
-  // sequence lookups (combiner -1, round 4; MI355_FUSED_SEQ=0 keeps them on the probe / partition / scatter chain): occurrence j
-  // is its own bag
-  constexpr int seq_env = 1;
+  // sequence lookups (combiner -1, round 4): occurrence j is its own bag
   const bool seq = combiner == -1;
-  bool pathc = part && part_env >= 2 && train && (combiner >= 0 || (seq && seq_env)) && hot_ws && bcsr && aligned16 &&
+  bool pathc = part && part_env >= 2 && train && combiner >= -1 && hot_ws && bcsr && aligned16 &&
                      emb_dim <= (4 << lg) && (seq || n <= 8 * num_bags) && value_dtype <= 1 && out_dtype <= 1 &&
                      num_bags < (1ll << 31) - 4096;
   // round 6: the partitioned stage is path (c) or nothing.  Round 2's form (a) -- the same record lists, merged by fused_part_kernel
@@ -2234,16 +2225,14 @@ int mi355_demb_forward_fused(
     return MI355_EINVAL;
   }
   // ---- eval / inference forward of one table with pooled output: ONE kernel (every lane probes its own keys; no dedup, no
-  //      unique numbering, no address array).  MI355_EVAL_FUSED=0 keeps the probe + gather pair.
-  constexpr int eval_env = 1;
-  if (!train && eval_env && n > 0 && num_tables >= 1 && num_tables <= kEvalMaxT && combiner >= -1 && aligned16 && !use_count &&
+  //      unique numbering, no address array).
+  if (!train && n > 0 && num_tables >= 1 && num_tables <= kEvalMaxT && combiner >= -1 && aligned16 && !use_count &&
       (find_policy == kConst || find_policy == kAssign || find_policy == kGlobalTimer) && (bucket_capacity & (bucket_capacity - 1)) == 0 &&
       value_dtype <= 1 && out_dtype <= 1 && num_buckets < (1ll << 31) && (combiner == -1 || n <= 8 * num_bags)) {
     int le = 3;
     while ((4 << le) < emb_dim && le < 6) ++le;
-    constexpr int eval_mt_env = 1;
     const bool mt = num_tables > 1;
-    if (emb_dim <= (4 << le) && (eval_mt_env || (!mt && combiner >= 0))) {
+    if (emb_dim <= (4 << le)) {
       RoctxRange rr("op:eval_lookup+gather_embedding");
       ProbeRefs pr;
       pr.keys = (const uint64_t*)keys; pr.t = a.t; pr.tbo = table_bucket_offsets; pr.table_ptrs = table_ptrs;
@@ -2289,9 +2278,8 @@ int mi355_demb_forward_fused(
     RoctxRange rr("op:fused_index(segmented_unique+storage_find+storage_insert+initializer)");
     // keys per tile / threads per block: one key per thread keeps every probe chain (digest vector -> key -> slot counter)
     // in flight at once; larger tiles cost fewer (tile, key) pairs = fewer device-scope atomics
-    constexpr int cfg_env = -1;
     // measured at C2 (360 K keys): 2048-key tiles / 1024 threads 33.5 us, 1024 / 1024 37.8 us, 1024 / 512 35.2 us
-    const int cfg = cfg_env >= 0 ? cfg_env : (n >= (64 << 10) ? 3 : 0);
+    const int cfg = n >= (64 << 10) ? 3 : 0;
 #define LAUNCH_PROBE(TILE, THREADS)                                                                                        \
   do {                                                                                                                     \
     const unsigned grid = (unsigned)ceil_div(n, TILE);                                                                     \

@@ -11,7 +11,6 @@ namespace mi355 {
 
 #include <stdlib.h>
 // occurrences above which a row takes the chunked path / CSR entries per task (one wave per task).
-// Tunable through MI355_HOT / MI355_CHUNK (read once per process) for profiling sweeps.
 static inline int hot_threshold() { return 4; }
 static inline int hot_chunk() { return 1024; }
 static inline int hot_wave() { return 128; }

@@ -55,7 +55,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 #define HSTU_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #endif
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;   // first-class 16-B value (HIP's uint4 struct arrays end up in scratch)
 
 #ifndef HSTU_XSTEP
@@ -70,21 +69,6 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;   // first-class 1
 constexpr int kBM = 128;  // query rows per workgroup (32 per wave)
 constexpr int kBN = 64;   // keys per tile
 
-#ifndef HSTU_QLDS_MIN
-#define HSTU_QLDS_MIN 512   // head dims from which the forward keeps its Q fragments in LDS instead of registers (none)
-#endif
-#ifndef HSTU_VTR
-#define HSTU_VTR 0           // forward: V tile row-major in LDS, V^T fragments through ds_read_b64_tr_b16 (no transposing commit).
-                            // OFF: correct on every head dim (tests), but no faster -- d = 256: 591 vs 603 TFLOP/s at L = 4096,
-                            // d = 128: +3 %; the transposing commit was not the bottleneck.  Kept for the backward rework.
-#endif
-#ifndef HSTU_BWD_TR
-#define HSTU_BWD_TR 1        // backward: GEMM 3/4/5 A operands by transpose reads from row-major tiles (no transposed copies)
-#endif
-#ifndef HSTU_DB_MIN
-#define HSTU_DB_MIN 1024    // head dims from which the forward double-buffers its K / V tiles in LDS (one barrier per tile).
-                            // OFF: measured slower at d = 256 (L = 4096: 512 vs 586 TFLOP/s single-buffered, same at L = 512)
-#endif
 
 struct AttnArgs {
   const uint16_t* q; const uint16_t* k; const uint16_t* v;
@@ -174,20 +158,11 @@ __device__ __forceinline__ void pin_agpr(f32x16_t (&c)[N]) {
 }
 template <int N> __device__ __forceinline__ void fence_v(f32x16_t (&)[N]) {}   // builtins: the compiler inserts the waits
 template <int N> __device__ __forceinline__ void fence_a(f32x16_t (&c)[N]) { pin_agpr(c); }
-// The kernels that run TWO waves per SIMD (256 registers per wave) must not mention AGPRs at all: one "+a" constraint makes hipcc
-// split the file 128 VGPRs + 128 AGPRs, and every value beyond the 128 -- the K / V / Q fragment sets of the S waves -- is then
-// parked in AGPRs and copied back with four v_accvgpr_read_b32 (+ s_nop) in front of EVERY MFMA that uses it: 50 clocks per MFMA
-// instead of 32 in the dK pass's S waves.  Without the pins the same kernels get up to 242 architectural VGPRs, no AGPRs, no copies.
-#ifndef HSTU_2W_AGPR
-#define HSTU_2W_AGPR 0
-#endif
-template <int N>
-__device__ __forceinline__ void pin_agpr_2w(f32x16_t (&c)[N]) {
-#if HSTU_2W_AGPR
-  pin_agpr(c);
-#endif
-}
-template <int N> __device__ __forceinline__ void fence_a_2w(f32x16_t (&c)[N]) { pin_agpr_2w(c); }
+// The kernels that run TWO waves per SIMD (256 registers per wave) must not mention AGPRs at all, so they never call pin_agpr():
+// one "+a" constraint makes hipcc split the file 128 VGPRs + 128 AGPRs, and every value beyond the 128 -- the K / V / Q fragment
+// sets of the S waves -- is then parked in AGPRs and copied back with four v_accvgpr_read_b32 (+ s_nop) in front of EVERY MFMA
+// that uses it: 50 clocks per MFMA instead of 32 in the dK pass's S waves.  Without the pins the same kernels get up to 242
+// architectural VGPRs, no AGPRs, no copies.
 
 // Row-side mask state of one query (causal case).  M(i, j) of the reference collapses to
 //   j <= jmax  and  (j < hlen  or  j >= jlo)
@@ -444,44 +419,14 @@ __device__ __forceinline__ float silu_scaled(float acc, float neg_alpha_log2e, f
   return acc * alpha_inv_scale * __builtin_amdgcn_rcpf(1.0f + t);
 }
 
-// rows [row0, row0+NR) of a [*, H, D] tensor -> LDS [NR][D+8] row-major (zeros beyond nvalid)
-template <int D, int NR>
-__device__ __forceinline__ void stage_rows(uint16_t* dst, const uint16_t* src, int64_t row_stride, int row0, int nvalid) {
-  constexpr int NCH = NR * D / 8;
-#pragma unroll
-  for (int ch = threadIdx.x; ch < NCH; ch += 256) {
-    const int r = ch / (D / 8), dc = ch % (D / 8);
-    uint4 t = make_uint4(0, 0, 0, 0);
-    if (row0 + r < nvalid) t = *reinterpret_cast<const uint4*>(src + (int64_t)(row0 + r) * row_stride + 8 * dc);
-    *reinterpret_cast<uint4*>(dst + r * (D + 8) + 8 * dc) = t;
-  }
-}
 #ifndef HSTU_TIMING
 #define HSTU_TIMING 0
 #endif
-#ifndef HSTU_XCH_NT
-#define HSTU_XCH_NT 0   // 1 = P / dS exchange tiles with non-temporal stores (dK pass) and loads (one-GEMM passes): written once, read once,
-                        // 0.5 GB each at 8 x 4096, they evict the Q / dO / K rows the same kernels stream through L2 again and again (TCC
-                        // counters: those rows miss L2 3-7 x, profiles/r04_pmc_hstu_traffic.txt).  Measured: -1..-2 % (8 x 4096 backward 648 against
-                        // 659-666 TFLOP/s, C3 140-149 against 137-144 us): off.
-#endif
-__device__ __forceinline__ void xch_store(u32x4_t* p, const u32x4_t& v) {
-#if HSTU_XCH_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ u32x4_t xch_load(const u32x4_t* p) {
-#if HSTU_XCH_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-#ifndef HSTU_X8_PROBE
-#define HSTU_X8_PROBE 0   // timing probes of the one-GEMM passes (results wrong): 1 = no fragment reads after the first batch, 2 = no exchange loads, 4 = no DMA after the first step
-#endif
+// P / dS exchange tiles: written once, read once, with plain stores and loads.  Measured and rejected: non-temporal ones (0.5 GB
+// each at 8 x 4096 evict the Q / dO / K rows the same kernels stream through L2 again and again, profiles/r04_pmc_hstu_traffic.txt),
+// -1..-2 % (8 x 4096 backward 648 against 659-666 TFLOP/s, C3 140-149 against 137-144 us).
+__device__ __forceinline__ void xch_store(u32x4_t* p, const u32x4_t& v) { *p = v; }
+__device__ __forceinline__ u32x4_t xch_load(const u32x4_t* p) { return *p; }
 #if HSTU_TIMING
 __device__ unsigned long long g_hstu_dbg[8 * 65536];
 __device__ __forceinline__ unsigned tick() {
@@ -500,21 +445,13 @@ __device__ __forceinline__ unsigned tick() {
 template <int D, bool kWin = false, bool kRab = false>   // kWin: local window, kRab: attention bias; variants of their own so that the plain path pays nothing
 __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   constexpr int KS = D + 8;    // padded K row (elements)
-  constexpr bool kVTR = HSTU_VTR != 0;
-  // V tile in LDS: kVTR -- row-major [kBN][VR] and the V^T fragments of GEMM 2 come out of the hardware transpose read
-  // (row stride D + 32 elements = 16 dwords mod 64: the 32 lanes of a half-wave hit 64 distinct banks); otherwise
-  // transposed [D][VS] by the committing threads (perm + 8-byte stores)
+  // V tile in LDS: transposed [D][VS] by the committing threads (perm + 8-byte stores).  Measured and rejected: a row-major V
+  // tile read back through ds_read_b64_tr_b16 (no faster: d = 256 591 vs 603 TFLOP/s at L = 4096, the transposing commit was not
+  // the bottleneck) and a double-buffered tile pair, one barrier per tile (L = 4096: 512 vs 586 TFLOP/s single-buffered).
   constexpr int VS = kBN + 8;  // padded V^T row (elements)
-  constexpr int VR = D == 32 ? 32 : D + 32;   // V row (elements): row stride = 16 dwords mod 64 (48 at d = 64: also conflict free)
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-  constexpr int TILE = kBN * KS + (kVTR ? kBN * VR : D * VS);   // elements of one staged (K, V) tile pair
-  // Optional (HSTU_DB_MIN, off by default): the tile pair DOUBLE-BUFFERED in LDS -- tile n+1 is committed into the other
-  // buffer inside the barrier interval in which tile n is consumed, one barrier per key tile instead of two.
-  constexpr bool kDB = D >= HSTU_DB_MIN;
-  uint16_t* Ks = smem;                 // [kBN][KS]           (of the tile being consumed)
+  uint16_t* Ks = smem;                 // [kBN][KS]
   uint16_t* Vt = smem + kBN * KS;      // [D][VS], key positions permuted inside every 16-group
-  constexpr bool QLDS = D >= HSTU_QLDS_MIN;      // Q fragments in LDS instead of 64 VGPRs (not used: 452 registers fit at d = 256)
-  uint16_t* Qs = smem + (kDB ? 2 : 1) * TILE;    // [kBM][KS] (QLDS only)
 
   const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks): see launch_fwd
   const int b = bs.b, h = bs.h;
@@ -583,10 +520,8 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   }
 
   // ---- Q fragments (B operand of GEMM 1): lane = (query l31, k half hi), 8 consecutive d per 16-slice
-  bf16x8_t qf[QLDS ? 1 : D / 16];
-  if constexpr (QLDS) {
-    stage_rows<D, kBM>(Qs, a.q + (int64_t)s.start * a.q_row + (int64_t)h * a.q_head, a.q_row, m0, Lq);
-  } else {
+  bf16x8_t qf[D / 16];
+  {
     const uint16_t* qp = a.q + (int64_t)(s.start + (qloc < Lq ? qloc : 0)) * a.q_row + (int64_t)h * a.q_head + 8 * hi;
 #pragma unroll
     for (int sl = 0; sl < D / 16; ++sl) {
@@ -610,7 +545,7 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   constexpr int KPT = (KCH + 255) / 256;      // per thread
   constexpr int VCH = (kBN / 4) * (D / 8);    // (4 keys x 8 d) blocks of the V tile
   constexpr int VPT = (VCH + 255) / 256;
-  u32x4_t kreg[KPT], vreg[kVTR ? 1 : VPT][4], vrow[kVTR ? KPT : 1];
+  u32x4_t kreg[KPT], vreg[VPT][4];
   // key j of the sequence: cached token (page table walk) or a token of k / v.  With a cache, k / v hold
   // [new history | candidates] per sequence and only the candidates are read from them (the history is in the cache).
   // (the keys that are not in the cache are the LAST Lk - cachelen rows of the sequence's k / v: key j >= cachelen is row Lq - Lk + j.
@@ -634,8 +569,7 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   // 40 loads per thread and tile -- as many VALU cycles as the tile's MFMAs take.
   constexpr int KROWS = 256 / (D / 8);        // K rows covered by the 256 threads per load round
   const uint16_t* k_thr = kbase + (tok0 + (int)threadIdx.x / (D / 8)) * a.k_row + 8 * ((int)threadIdx.x % (D / 8));
-  const uint16_t* vr_thr = vbase + (tok0 + (int)threadIdx.x / (D / 8)) * a.v_row + 8 * ((int)threadIdx.x % (D / 8));
-  const int64_t kstep = (int64_t)KROWS * a.k_row, vrstep = (int64_t)KROWS * a.v_row;
+  const int64_t kstep = (int64_t)KROWS * a.k_row;
   const uint16_t* v_thr;
   {
     const int kgpos = (int)threadIdx.x % (kBN / 4), g16 = kgpos >> 2, pg = kgpos & 3;
@@ -648,20 +582,14 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
       const uint16_t* kp = k_thr + (int64_t)n0 * a.k_row;
 #pragma unroll
       for (int i = 0; i < KPT; ++i) kreg[i] = *reinterpret_cast<const u32x4_t*>(kp + i * kstep);
-      if constexpr (kVTR) {
-        const uint16_t* vp = vr_thr + (int64_t)n0 * a.v_row;
+      const uint16_t* vp = v_thr + (int64_t)n0 * a.v_row;
 #pragma unroll
-        for (int i = 0; i < KPT; ++i) vrow[i] = *reinterpret_cast<const u32x4_t*>(vp + i * vrstep);
-      } else {
-        const uint16_t* vp = v_thr + (int64_t)n0 * a.v_row;
+      for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-          for (int i = 0; i < VPT; ++i)
-            if (VCH % 256 == 0 || (int)threadIdx.x + 256 * i < VCH)
-              vreg[i][kk] = *reinterpret_cast<const u32x4_t*>(vp + 8 * (256 / (kBN / 4)) * i);
-          vp += a.v_row;
-        }
+        for (int i = 0; i < VPT; ++i)
+          if (VCH % 256 == 0 || (int)threadIdx.x + 256 * i < VCH)
+            vreg[i][kk] = *reinterpret_cast<const u32x4_t*>(vp + 8 * (256 / (kBN / 4)) * i);
+        vp += a.v_row;
       }
       return;
     }
@@ -673,15 +601,6 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
       const int row = n0 + key < s.L ? n0 + key : s.L - 1;
       if (KCH % 256 == 0 || ch < KCH) kreg[i] = *reinterpret_cast<const u32x4_t*>(kv_row(row, 0) + 8 * dc);
     }
-    if constexpr (kVTR) {
-#pragma unroll
-      for (int i = 0; i < KPT; ++i) {   // V rows exactly like K rows
-        const int ch = threadIdx.x + 256 * i;
-        const int key = ch / (D / 8), dc = ch % (D / 8);
-        const int row = n0 + key < s.L ? n0 + key : s.L - 1;
-        if (KCH % 256 == 0 || ch < KCH) vrow[i] = *reinterpret_cast<const u32x4_t*>(kv_row(row, 1) + 8 * dc);
-      }
-    } else {
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
       const int ch = threadIdx.x + 256 * i;
@@ -695,7 +614,6 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
         if (VCH % 256 == 0 || ch < VCH) vreg[i][kk] = *reinterpret_cast<const u32x4_t*>(kv_row(row, 1) + 8 * dc);
       }
     }
-    }
   };
   auto commit = [&](uint16_t* Kd, uint16_t* Vd) {
 #pragma unroll
@@ -703,15 +621,6 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
       const int ch = threadIdx.x + 256 * i;
       const int key = ch / (D / 8), dc = ch % (D / 8);
       if (KCH % 256 == 0 || ch < KCH) *reinterpret_cast<u32x4_t*>(Kd + key * KS + 8 * dc) = kreg[i];
-    }
-    if constexpr (kVTR) {
-#pragma unroll
-      for (int i = 0; i < KPT; ++i) {
-        const int ch = threadIdx.x + 256 * i;
-        const int key = ch / (D / 8), dc = ch % (D / 8);
-        if (KCH % 256 == 0 || ch < KCH) *reinterpret_cast<u32x4_t*>(Vd + key * VR + 8 * dc) = vrow[i];
-      }
-      return;
     }
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
@@ -733,33 +642,11 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
 
   // A operand of GEMM 2: V^T[32 d of tile dt][16 keys of slice ks], lane (d = l31, k half = hi) holds the 8 keys
   // (j&3) + 8*(j>>2) + 4*hi of the slice (the register order of the S accumulator, see ew()).
-  // kVTR: two hardware transpose reads per fragment.  Within a 16-lane group the read returns to lane l column l of the
-  // 4 x 16 block whose row (i>>2), columns 4*(i&3)..+3 lane i points at: out_l[j] = in_{4j + (l>>2)}[l & 3] (probed on
-  // gfx950).  Groups: lanes 16g..16g+15 = d half (g & 1), k half (g >> 1) of the fragment.
-  const int tr_il = lane & 15;
-  const int tr_off = ((4 * hi + (tr_il >> 2)) * VR + 16 * ((lane >> 4) & 1) + 4 * (tr_il & 3));   // elements, inside (slice, d tile)
   auto v_frag = [&](const uint16_t* Vb, int dt, int ks) -> bf16x8_t {
-    if constexpr (kVTR) {
-      typedef short v4s_t __attribute__((ext_vector_type(4)));
-      typedef __attribute__((address_space(3))) v4s_t* lds_v4s_t;
-      const uint16_t* p0 = Vb + (16 * ks) * VR + 32 * dt + tr_off;
-      const v4s_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(p0));
-      const v4s_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(p0 + 8 * VR));
-      typedef short v8s_t __attribute__((ext_vector_type(8)));
-      const v8s_t r = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-      return __builtin_bit_cast(bf16x8_t, r);
-    } else {
-      return *reinterpret_cast<const bf16x8_t*>(Vb + (32 * dt + l31) * VS + 16 * ks + 8 * hi);
-    }
+    return *reinterpret_cast<const bf16x8_t*>(Vb + (32 * dt + l31) * VS + 16 * ks + 8 * hi);
   };
 
-  if (n_end > n_beg) {
-    fetch(n_beg);
-    if constexpr (kDB) {
-      commit(smem, smem + kBN * KS);
-      if (n_beg + kBN < n_end) fetch(n_beg + kBN);
-    }
-  }
+  if (n_end > n_beg) fetch(n_beg);
   int it = 0;
 #if HSTU_TIMING
   unsigned tsum[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -768,27 +655,16 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   for (int n0 = n_beg; n0 < n_end; n0 += kBN, ++it) {
     pin_agpr(acc_o);
     TICK(t0);
-    __syncthreads();   // kDB: everyone is done with the other buffer, and this tile's commit (previous interval) is visible
-    if constexpr (kDB) {
-      uint16_t* cur = smem + (it & 1) * TILE;
-      uint16_t* oth = smem + ((it & 1) ^ 1) * TILE;
-      Ks = cur;
-      Vt = cur + kBN * KS;
-      if (n0 + kBN < n_end) {
-        commit(oth, oth + kBN * KS);                     // tile n0 + kBN (in registers since the previous interval)
-        if (n0 + 2 * kBN < n_end) fetch(n0 + 2 * kBN);
-      }
-    } else {
-      TICK(t1);
-      commit(Ks, Vt);
-      pin_agpr(acc_o);
-      TICK(t2);
-      __syncthreads();
-      TICK(t3);
-      if (n0 + kBN < n_end) fetch(n0 + kBN);
-      TICK(t4);
-      TACC(0, t0, t1); TACC(1, t1, t2); TACC(2, t2, t3); TACC(3, t3, t4);
-    }
+    __syncthreads();
+    TICK(t1);
+    commit(Ks, Vt);
+    pin_agpr(acc_o);
+    TICK(t2);
+    __syncthreads();
+    TICK(t3);
+    if (n0 + kBN < n_end) fetch(n0 + kBN);
+    TICK(t4);
+    TACC(0, t0, t1); TACC(1, t1, t2); TACC(2, t2, t3); TACC(3, t3, t4);
     pin_agpr(acc_o);
     if (!wave_live || n0 >= w_end || n0 < w_beg) continue;
     if constexpr (kRab) { if (!func_ext_hits(wx, n0, n0 + kBN)) continue; }     // (a gap between the prefix and the bands)
@@ -807,8 +683,7 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int u = 0; u < SLB; ++u) {
           const int sl = SLB * bi + u;
-          if constexpr (QLDS) qfr[buf][u] = *reinterpret_cast<const bf16x8_t*>(Qs + (32 * wv + l31) * KS + 16 * sl + 8 * hi);
-          else qfr[buf][u] = qf[sl];
+          qfr[buf][u] = qf[sl];
 #pragma unroll
           for (int t = 0; t < 2; ++t)
             kfr[buf][u][t] = *reinterpret_cast<const bf16x8_t*>(Ks + (32 * t + l31) * KS + 16 * sl + 8 * hi);
@@ -884,21 +759,15 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
           vfr[buf][u] = v_frag(Vt, dt0 + u, ks);
       };
       load_v(0, 0);
-      constexpr bool kPipe = true;
       bf16x8_t pf[4];
       pf[0] = ew(0);
-      if constexpr (!kPipe) { pf[1] = ew(1); pf[2] = ew(2); pf[3] = ew(3); }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int bi = 0; bi < NBAT2; ++bi) {
         const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
         const bool last_of_ks = (bi % (NDT / DB)) == (NDT / DB) - 1;
         if (bi + 1 < NBAT2) load_v(bi + 1, (bi + 1) & 1);
-        if constexpr (kPipe) {
-          if (last_of_ks && ks + 1 < 4) pf[ks + 1] = ew(ks + 1);   // independent of this batch's MFMAs: fills their shadow
-        } else {
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        if (last_of_ks && ks + 1 < 4) pf[ks + 1] = ew(ks + 1);   // independent of this batch's MFMAs: fills their shadow
 #pragma unroll
         for (int u = 0; u < DB; ++u) mfma_a(acc_o[dt0 + u], vfr[bi & 1][u], pf[ks]);
         __builtin_amdgcn_sched_barrier(0);
@@ -1002,7 +871,7 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Forward with LDS-DMA staging (the default at head dim 256 with contiguous keys; MI355_HSTU_DMA=0 turns it off).  Same GEMMs, masks and register
+// Forward with LDS-DMA staging (head dim 256 with contiguous keys: the kernels below).  Same GEMMs, masks and register
 // layouts as hstu_fwd_kernel; what differs is how a (K, V) tile reaches LDS.  The stamps of the register-staged kernel
 //  put 1.2 K cycles per tile into issuing 16 global loads per wave and 0.9 K into writing the
 // prefetched registers to LDS (K rows + the transposing V commit), against 2 K cycles of MFMA; `global_load_lds_dwordx4`
@@ -1036,39 +905,33 @@ typedef __attribute__((address_space(1))) const void* glb_void_t;
 // iteration.  LDS = K ring 2 x 32 KB + V ring 2 x 32 KB + P ring 2 x 4 x 4 KB = 160 KB, all of it.
 // The K / V images and swizzles are the ones described above.
 // ---------------------------------------------------------------------------------------------------
-#ifndef HSTU_PC_SDMA
-#define HSTU_PC_SDMA 0   // LDS-DMA instructions per tile and tensor issued by each S wave (of 32; the O waves issue the rest)
-#endif
-#ifndef HSTU_PC_DSPREAD
-#define HSTU_PC_DSPREAD 0   // O waves: 0 = their LDS-DMA share in one burst behind the barrier, n = dealt over the first n MFMA batches of GEMM 2
-#endif
+// Row blocks in (heavy, light) PAIRS per workgroup (kPair; dense batches): one workgroup takes the z-th heaviest and the z-th
+// lightest row block of a (sequence, head) column and runs them as ONE tile stream -- block A's key tiles, then block B's --
+// through the same rings.  Under a causal mask every pair carries the same number of key tiles (C3: 8 + 2 and 6 + 4 of a
+// column's four blocks; 32 x 4096: 33 each), so the grid is balanced by construction and, at C3, exactly one workgroup per CU;
+// the second block's first K tile is prefetched under the first block's last tile, the O waves store block A's rows while the
+// S waves already work on block B's first tile, and the pipeline fills and drains once per pair instead of once per block.
+// Without kPair a workgroup takes one row block (grid (H, B, blocks)).  Same tiles, same MFMA order, same roundings either
+// way: bit-identical output.
+// Measured and rejected: part of the DMA issued by the S waves, the O waves' DMA share dealt over their first MFMA batches
+// instead of one burst behind the barrier, and a static priority (s_setprio) for either role.
+// ---------------------------------------------------------------------------------------------------
 #ifndef HSTU_PC_KBUF
 #define HSTU_PC_KBUF 3   // S waves: K fragment batches (4 slices) in registers, KBUF - 1 of them in flight ahead of the MFMAs
 #endif
 #ifndef HSTU_PC_VBUF
 #define HSTU_PC_VBUF 3   // O waves: V^T fragment batches likewise
 #endif
-#ifndef HSTU_PC_PROBE
-#define HSTU_PC_PROBE 0  // timing probes, results WRONG on purpose: 1 = SiLU without transcendentals, 2 = no SiLU (pack the raw S), 4 = DMA of
-                         // the first two tiles only, 8 = no GEMM 2 MFMAs, 16 = no GEMM 1 MFMAs
-#endif
-#ifndef HSTU_PC_PRIO
-#define HSTU_PC_PRIO 0   // static wave priority: 1 = the O waves (the younger half) at s_setprio 1, 2 = the S waves
-#endif
-template <int D, bool kWin>
-__global__ void __launch_bounds__(512) hstu_fwd_pc_kernel(AttnArgs a) {
+template <int D, bool kWin, bool kPair>
+__global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
   static_assert(D == 256, "rows of 32 chunks");
-  constexpr int CPR = D / 8;            // 16-byte chunks per row
-  constexpr int RPI = 64 / CPR;         // rows per DMA wave-instruction (1 KB)
-  constexpr int ROWB = D;               // row stride in LDS (elements): unpadded
-  constexpr int TENS = kBN * ROWB;      // elements of one K (or V) tile
-  constexpr int NINS = kBN / RPI;       // DMA instructions per tile and tensor (32)
+  constexpr int CPR = D / 8, RPI = 64 / CPR, ROWB = D, TENS = kBN * ROWB, NINS = kBN / RPI;
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];   // [K 0 | K 1 | V 0 | V 1 | P 0 | P 1]
   uint16_t* const Kring = smem;
   uint16_t* const Vring = smem + 2 * TENS;
   uint16_t* const Pring = smem + 4 * TENS;   // [2][4 pairs][4 key slices][64 lanes] x 16 B
 
-  const BlockSeq bs = seq_head_of_block(a);
+  const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks) or, kPair, (H, B, ceil(blocks / 2)): z = the rank inside the column
   const int b = bs.b, h = bs.h;
   SeqInfo s;
   s.start = bs.start;
@@ -1077,8 +940,9 @@ __global__ void __launch_bounds__(512) hstu_fwd_pc_kernel(AttnArgs a) {
   s.L = a.cu_seqlens_k ? a.cu_seqlens_k[b + 1] - kstart : Lq;
   const int dq = s.L - Lq;
   const int nblk = (Lq + kBM - 1) / kBM;
-  if (bs.z >= nblk || dq < 0) return;
-  const int m0 = row_block_of_rank(bs.z, nblk, a, b) * kBM;
+  if ((kPair ? 2 * bs.z : bs.z) >= nblk || dq < 0) return;
+  const int rank0 = bs.z, rank1 = kPair ? nblk - 1 - bs.z : bs.z;
+  const bool two = kPair && rank1 > rank0;
   s.has_ctx = a.num_contexts != nullptr;
   s.has_tgt = a.num_targets != nullptr;
   s.c = s.has_ctx ? a.num_contexts[b] : 0;
@@ -1088,398 +952,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_pc_kernel(AttnArgs a) {
   const int lane = lane_id(), hi = lane >> 5, l31 = lane & 31;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int role = wv >> 2, pw = wv & 3;    // role 0: S wave, 1: O wave; pw: the pair's 32-row group
-  const int qrow0 = m0 + 32 * pw, qloc = qrow0 + l31, qi = dq + qloc;
-  const bool wave_live = qrow0 < Lq;
-  int last_row = dq + (m0 + kBM - 1 < Lq - 1 ? m0 + kBM - 1 : Lq - 1);
-  int n_end = s.L;
-  if (a.causal) {
-    n_end = last_row + 1;
-    if (s.has_ctx && dq + m0 < s.c && s.hlen > n_end) n_end = s.hlen;
-  }
-  if (kWin) n_end = band_key_end(a, last_row, n_end);
-  const int n_beg = kWin ? band_key_begin(a, dq + m0, kBN) : 0;
-  int w_last = dq + (qrow0 + 31 < Lq - 1 ? qrow0 + 31 : Lq - 1);
-  int w_end = s.L;
-  if (a.causal) {
-    w_end = w_last + 1;
-    if (s.has_ctx && dq + qrow0 < s.c && s.hlen > w_end) w_end = s.hlen;
-  }
-  if (kWin) w_end = band_key_end(a, w_last, w_end);
-  const int w_beg = kWin ? band_key_begin(a, dq + qrow0, kBN) : 0;
-  const int T = n_end > n_beg ? (n_end - n_beg + kBN - 1) / kBN : 0;   // key tiles of the block
-
-  // ---- the DMA of one tile of one tensor: instruction j moves rows 2 j, 2 j + 1.  S wave pw issues instructions
-  // [HSTU_PC_SDMA pw, + HSTU_PC_SDMA), O wave pw the rest dealt evenly.  Lane -> (row inside the instruction, LDS chunk slot p);
-  // the lane fetches global chunk p ^ swizzle(row).  Addressing: a wave-uniform 64-bit row base (SGPR arithmetic) plus a
-  // per-lane 32-bit offset that depends on the instruction only through j mod 8 -- NMY registers per tensor computed once
-  // (64-bit per-lane pointers per instruction cost 2 multiplies and a spilled pointer each, and the reload's vmcnt(0)
-  // serialised the DMAs).  Rows past the sequence end (the sequence's last tile only) are read clamped: their P is zero.
-  const uint16_t* kg = a.k + (int64_t)kstart * a.k_row + (int64_t)h * a.k_head;
-  const uint16_t* vg = a.v + (int64_t)kstart * a.v_row + (int64_t)h * a.v_head;
-  const int dma_r = lane / CPR, dma_p = lane % CPR;
-  constexpr int NS = HSTU_PC_SDMA, NO = (NINS - 4 * NS) / 4;
-  static_assert(4 * NS + 4 * NO == NINS, "the instruction split must cover the tile");
-  constexpr int NMY = NS > NO ? NS : NO;
-  const int j_first = role == 0 ? NS * pw : 4 * NS + NO * pw;
-  const int n_my = role == 0 ? NS : NO;
-  uint32_t kvoff[NMY], vvoff[NMY];
-#pragma unroll
-  for (int u = 0; u < NMY; ++u) {
-    const int r = RPI * (j_first + u) + dma_r;
-    kvoff[u] = (uint32_t)dma_r * (uint32_t)a.k_row * 2u + 16u * (uint32_t)(dma_p ^ (r & 15));
-    vvoff[u] = (uint32_t)dma_r * (uint32_t)a.v_row * 2u + 16u * (uint32_t)(dma_p ^ ((r & 3) << 2));
-  }
-  // The DMA instruction is issued from inline asm: hipcc models the builtin as an LDS store in flight and puts a
-  // vmcnt(0) in front of the next transpose read of ANY LDS address (seen in the removed one-kind DMA forward's GEMM 2: the prefetch
-  // it was meant to overlap is drained first).  Here the completion is counted by hand: vmcnt(0) + barrier at the loop head.
-  bool dma_on = true;
-  auto dma16 = [&](const char* sbase, uint32_t voff, uint32_t lds_byte) {
-    if ((HSTU_PC_PROBE & 4) && !dma_on) return;
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_byte), "s"(sbase) : "memory");
-  };
-  auto issue_dma = [&](const uint16_t* g, int64_t g_row, const uint32_t (&voff)[NMY], uint16_t* ring, int tile, int u0, int u1) {
-    const int n0 = n_beg + kBN * tile;                                // (instructions [u0, u1) of this wave's share)
-    const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t)(ring + (tile & 1) * TENS + RPI * j_first * ROWB));
-    if (n0 + kBN <= s.L) {
-      const char* sb = reinterpret_cast<const char*>(g + (int64_t)(n0 + RPI * j_first) * g_row);
-      const int64_t step = (int64_t)RPI * g_row * 2;
-#pragma unroll
-      for (int u = 0; u < NMY; ++u)
-        if (u >= u0 && u < u1 && u < n_my) dma16(sb + u * step, voff[u], dst + u * (RPI * ROWB * 2));
-    } else {
-      const uint32_t rowterm = (uint32_t)dma_r * (uint32_t)g_row * 2u;
-#pragma unroll
-      for (int u = 0; u < NMY; ++u)
-        if (u >= u0 && u < u1 && u < n_my) {
-          const int row0 = n0 + RPI * (j_first + u);                   // wave-uniform: the instruction's first row
-          const int rowc = row0 < s.L ? row0 : s.L - 1;                // clamped to the sequence
-          const uint32_t drop = row0 + 1 < s.L ? 0u : 0xffffffffu;     // its second row is past the end: read the first again
-          dma16(reinterpret_cast<const char*>(g + (int64_t)rowc * g_row), voff[u] - (rowterm & drop), dst + u * (RPI * ROWB * 2));
-        }
-    }
-  };
-
-  // ---- S wave state: Q fragments (B operand of GEMM 1) and the row mask
-  bf16x8_t qf[D / 16];
-  const float nal2e = -a.alpha * 1.44269504088896f, ais = a.alpha * a.inv_scale;
-  const RowMask rm = row_mask(qi < s.L ? qi : s.L - 1, s, a.causal, a.group);
-  // ---- O wave state
-  f32x16_t acc_o[D / 32];
-
-  if (T > 0) issue_dma(kg, a.k_row, kvoff, Kring, 0, 0, NMY);
-  if (HSTU_PC_PRIO != 0 && role == (HSTU_PC_PRIO == 1 ? 1 : 0)) __builtin_amdgcn_s_setprio(1);
-
-  // fragment addresses under the swizzles described above
-  const int kx = l31 & 15;
-  const int il = lane & 15, g1 = (lane >> 4) & 1, vq = il >> 2;
-  const int v_row_off = (4 * hi + vq) * ROWB + 4 * (il & 1);
-  const int v_chunk_lo = 2 * g1 + ((il & 3) >> 1);
-  auto v_frag = [&](const uint16_t* Vb, int dt, int ks) -> bf16x8_t {
-    typedef short v4s_t __attribute__((ext_vector_type(4)));
-    typedef short v8s_t __attribute__((ext_vector_type(8)));
-    typedef __attribute__((address_space(3))) v4s_t* lds_v4s_t;
-    const uint16_t* p0 = Vb + (16 * ks) * ROWB + v_row_off + 8 * ((4 * (dt ^ vq)) + v_chunk_lo);
-    const v4s_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(p0));
-    const v4s_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(p0 + 8 * ROWB));
-    const v8s_t r = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-    return __builtin_bit_cast(bf16x8_t, r);
-  };
-
-  // Two loops, one per role, with the same trip count and ONE barrier per iteration each (a single loop with the role
-  // test inside keeps Q and the O accumulator live together: 192 registers before anything else, 363 spilled).
-#if HSTU_TIMING
-  unsigned tsum[7] = {0, 0, 0, 0, 0, 0, 0};   // wait for own DMA, barrier, DMA issue, role, GEMM 1, SiLU + hand-off | GEMM 2, tiles
-  const unsigned t_start = tick();
-  auto t_dump = [&]() {
-    const unsigned t_end = tick();
-    if (lane == 0) {
-      const int blk = ((int)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-      unsigned long long* d = g_hstu_dbg + ((size_t)(blk * 8 + wv) % 65536) * 8;
-      for (int i = 0; i < 7; ++i) d[i] = tsum[i];
-      d[6] |= (unsigned long long)role << 32;
-      d[7] = t_end - t_start;
-    }
-  };
-#endif
-  auto head = [&](int it) {
-    if (HSTU_PC_PROBE & 4) dma_on = it < 1;
-    TICK(t0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces (K tile it, V tile it - 1) have landed ...
-    TICK(t1);
-    __syncthreads();                                    // ... everyone's have, P[it - 1] is written, the other buffers are free
-    TICK(t2);
-    if (role == 0 || HSTU_PC_DSPREAD == 0) {
-      if (it + 1 < T) issue_dma(kg, a.k_row, kvoff, Kring, it + 1, 0, NMY);
-      if (it < T) issue_dma(vg, a.v_row, vvoff, Vring, it, 0, NMY);
-    }
-    TICK(t3);
-    TACC(0, t0, t1); TACC(1, t1, t2); TACC(2, t2, t3);
-  };
-  if (role == 0) {
-    // =========================== S wave: tile `it` -> P ring slot it & 1 ===========================
-    {
-      const uint16_t* qp = a.q + (int64_t)(s.start + (qloc < Lq ? qloc : 0)) * a.q_row + (int64_t)h * a.q_head + 8 * hi;
-#pragma unroll
-      for (int sl = 0; sl < D / 16; ++sl) {
-        uint4 t = make_uint4(0, 0, 0, 0);
-        if (qloc < Lq) t = *reinterpret_cast<const uint4*>(qp + 16 * sl);
-        qf[sl] = *reinterpret_cast<bf16x8_t*>(&t);
-      }
-    }
-    for (int it = 0; it <= T; ++it) {
-      head(it);
-      const int n0 = n_beg + kBN * it;
-      if (it >= T || !wave_live || n0 >= w_end || n0 < w_beg) continue;
-      const uint16_t* Ks = Kring + (it & 1) * TENS;
-      TICK(t5);
-      // mask mode of the tile (wave-uniform): 0 = every key visible, 1 = key <= jmax only (plain causal / sequence end:
-      // one compare per element against a per-lane threshold), 2 = the general rule (contextual / target rows, windows)
-      const bool full = a.causal && s.wl < 0 && (n0 + kBN - 1 <= dq + qrow0) && (!s.has_ctx || dq + qrow0 >= s.c) && (!s.has_tgt || n0 + kBN - 1 < s.hlen);
-      const int mode = full ? 0 : ((!s.has_ctx && !s.has_tgt && s.wl < 0) ? 1 : 2);
-      u32x4_t* pdst = reinterpret_cast<u32x4_t*>(Pring) + (((it & 1) * 4 + pw) * 4) * 64 + lane;
-      // One tile, software-pipelined inside the wave: GEMM 1 of the second 32-key sub-tile carries the SiLU of the first
-      // (one element pair per two MFMAs), so that only the second sub-tile's SiLU runs without MFMAs of this wave.
-      auto tile = [&](auto modec) {
-        constexpr int kMode = decltype(modec)::value;
-        constexpr int SLB = 4, NBAT = (D / 16) / SLB, NKB = HSTU_PC_KBUF;   // fragment batches of 4 slices, NKB - 1 batches in flight
-        f32x16_t acc_s[2];
-        // (measured and rejected: two accumulator chains per sub-tile -- even / odd slices of d, added in the SiLU -- so that
-        // consecutive MFMAs never share an accumulator: 805 vs 841 TFLOP/s at 32 x 4096; the chain is not what paces GEMM 1)
-        const int th = rm.jmax - n0 - 4 * hi;       // kMode 1: element (t, rr) is visible iff 32 t + (rr & 3) + 8 (rr >> 2) <= th
-        // NE elements r0 .. r0 + NE - 1 of sub-tile t -> NE / 2 packed P words, stage by stage over the group
-        auto group = [&](auto nec, int t, int r0, uint32_t* out) {
-          constexpr int NE = decltype(nec)::value;
-          float x[NE], e[NE], y[NE];
-#pragma unroll
-          for (int i = 0; i < NE; ++i) x[i] = acc_s[t][r0 + i];
-#pragma unroll
-          for (int i = 0; i < NE; ++i) e[i] = x[i] * nal2e;
-#pragma unroll
-          for (int i = 0; i < NE; ++i) e[i] = (HSTU_PC_PROBE & 1) ? e[i] * 0.5f : __builtin_amdgcn_exp2f(e[i]);
-#pragma unroll
-          for (int i = 0; i < NE; ++i) e[i] = 1.0f + e[i];
-#pragma unroll
-          for (int i = 0; i < NE; ++i) e[i] = (HSTU_PC_PROBE & 1) ? e[i] * 0.25f : __builtin_amdgcn_rcpf(e[i]);
-#pragma unroll
-          for (int i = 0; i < NE; ++i) y[i] = (HSTU_PC_PROBE & 2) ? x[i] : x[i] * ais * e[i];
-          if (kMode != 0) {
-#pragma unroll
-            for (int i = 0; i < NE; ++i) {
-              const int rr = r0 + i, off = 32 * t + (rr & 3) + 8 * (rr >> 2);
-              const bool ok = kMode == 1 ? off <= th : key_ok(n0 + off + 4 * hi, rm);
-              y[i] = ok ? y[i] : 0.f;
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < NE; i += 2) out[i >> 1] = pack_bf16(y[i], y[i + 1]);
-        };
-        bf16x8_t kfr[NKB][SLB];
-        auto load_b = [&](int gb) {               // global batch gb = NBAT t + bi
-          const int t = gb / NBAT, bi = gb % NBAT;
-#pragma unroll
-          for (int u = 0; u < SLB; ++u) {
-            const int sl = SLB * bi + u;
-            const int ch = ((2 * sl) ^ (kx & 14)) + (hi ^ (kx & 1));
-            kfr[gb % NKB][u] = *reinterpret_cast<const bf16x8_t*>(Ks + (32 * t + l31) * ROWB + 8 * ch);
-          }
-        };
-        auto mfma_b = [&](int gb) {
-          const int t = gb / NBAT, bi = gb % NBAT;
-#pragma unroll
-          for (int u = 0; u < SLB; ++u) {
-            f32x16_t& c = acc_s[t];
-            if (HSTU_PC_PROBE & 16) { if (bi == 0) for (int z = 0; z < 16; ++z) c[z] = __builtin_bit_cast(float, __builtin_bit_cast(u32x4_t, kfr[0][0])[z & 3]); }
-            else if (bi == 0 && u == 0) mfma_v0(c, kfr[gb % NKB][u], qf[SLB * bi + u]);
-            else mfma_v(c, kfr[gb % NKB][u], qf[SLB * bi + u]);
-          }
-        };
-#pragma unroll
-        for (int gb = 0; gb < NKB - 1; ++gb) load_b(gb);
-        // ---- sub-tile 0: MFMAs only
-#pragma unroll
-        for (int gb = 0; gb < NBAT; ++gb) {
-          if (gb + NKB - 1 < 2 * NBAT) load_b(gb + NKB - 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma_b(gb);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        TICK(t6);
-        TACC(4, t5, t6);
-        // ---- sub-tile 1: MFMAs + the SiLU of sub-tile 0 (4 elements per batch of 4 MFMAs)
-        uint32_t pk[8];
-#pragma unroll
-        for (int gb = NBAT; gb < 2 * NBAT; ++gb) {
-          const int bi = gb - NBAT;
-          if (gb + NKB - 1 < 2 * NBAT) load_b(gb + NKB - 1);
-          mfma_b(gb);
-          group(std::integral_constant<int, 4>{}, 0, 4 * bi, pk + 2 * bi);
-          if (bi == 1) pdst[0 * 64] = u32x4_t{pk[0], pk[1], pk[2], pk[3]};
-          if (bi == 3) pdst[1 * 64] = u32x4_t{pk[4], pk[5], pk[6], pk[7]};
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        TICK(t6b);
-        TACC(3, t6, t6b);
-        // ---- the SiLU of sub-tile 1
-        group(std::integral_constant<int, 8>{}, 1, 0, pk);
-        pdst[2 * 64] = u32x4_t{pk[0], pk[1], pk[2], pk[3]};
-        group(std::integral_constant<int, 8>{}, 1, 8, pk + 4);
-        pdst[3 * 64] = u32x4_t{pk[4], pk[5], pk[6], pk[7]};
-        TICK(t7);
-        TACC(5, t6b, t7);
-      };
-      if (mode == 0) tile(std::integral_constant<int, 0>{});
-      else if (mode == 1) tile(std::integral_constant<int, 1>{});
-      else tile(std::integral_constant<int, 2>{});
-#if HSTU_TIMING
-      tsum[6] += 1;
-#endif
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (no DMA may be in flight into LDS when the block retires)
-#if HSTU_TIMING
-    t_dump();
-#endif
-    return;
-  }
-  {
-    // =========================== O wave: tile `it - 1` from P ring slot (it - 1) & 1 ===========================
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc_o[dt][r] = 0.f;
-    for (int it = 0; it <= T; ++it) {
-      pin_agpr_2w(acc_o);
-      head(it);
-      pin_agpr_2w(acc_o);
-      const int tl = it - 1, n0 = n_beg + kBN * tl;
-      const bool live = it != 0 && wave_live && n0 < w_end && n0 >= w_beg;
-      // HSTU_PC_DSPREAD: this wave's DMA share (K tile it + 1, V tile it) is dealt over the first MFMA batches of GEMM 2
-      // when there is a GEMM 2 and both tiles lie inside the sequence (no clamped rows); otherwise one burst, as at the head.
-      const int nk0 = n_beg + kBN * (it + 1), nv0 = n_beg + kBN * it;
-      const bool spread = HSTU_PC_DSPREAD != 0 && live && it + 1 < T && nk0 + kBN <= s.L;   // (then V tile `it` is inside as well)
-      if (HSTU_PC_DSPREAD != 0 && !spread) {
-        if (it + 1 < T) issue_dma(kg, a.k_row, kvoff, Kring, it + 1, 0, NMY);
-        if (it < T) issue_dma(vg, a.v_row, vvoff, Vring, it, 0, NMY);
-      }
-      if (!live) continue;
-      const uint16_t* Vt = Vring + (tl & 1) * TENS;
-      TICK(t6);
-      const u32x4_t* psrc = reinterpret_cast<const u32x4_t*>(Pring) + (((tl & 1) * 4 + pw) * 4) * 64 + lane;
-      {
-        // (ONE copy of GEMM 2 with the DMA statements behind a wave-uniform test: two specialised copies made hipcc carry
-        // the accumulator through a phi and spill it)
-        const char* kb = reinterpret_cast<const char*>(kg + (int64_t)(nk0 + RPI * j_first) * a.k_row);
-        const char* vb = reinterpret_cast<const char*>(vg + (int64_t)(nv0 + RPI * j_first) * a.v_row);
-        const int64_t kstep = (int64_t)RPI * a.k_row * 2, vstep = (int64_t)RPI * a.v_row * 2;
-        const uint32_t kdst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t)(Kring + ((it + 1) & 1) * TENS + RPI * j_first * ROWB));
-        const uint32_t vdst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t)(Vring + (it & 1) * TENS + RPI * j_first * ROWB));
-        bf16x8_t pf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) pf[ks] = __builtin_bit_cast(bf16x8_t, psrc[ks * 64]);
-        constexpr int NDT = D / 32, DB = 4, NVB = HSTU_PC_VBUF;
-        constexpr int NBAT2 = 4 * (NDT / DB);
-        bf16x8_t vfr[NVB][DB];
-        auto load_v = [&](int bi) {
-          const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
-#pragma unroll
-          for (int u = 0; u < DB; ++u) vfr[bi % NVB][u] = v_frag(Vt, dt0 + u, ks);
-        };
-#pragma unroll
-        for (int bi = 0; bi < NVB - 1; ++bi) load_v(bi);
-        pin_agpr_2w(acc_o);
-#pragma unroll
-        for (int bi = 0; bi < NBAT2; ++bi) {
-          const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
-          if (bi + NVB - 1 < NBAT2) load_v(bi + NVB - 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int u = 0; u < DB; ++u) {
-            if (HSTU_PC_PROBE & 8) { if (u == 0 && bi == 0) acc_o[0][0] += __builtin_bit_cast(float, __builtin_bit_cast(u32x4_t, vfr[bi % NVB][0])[0] ^ __builtin_bit_cast(u32x4_t, pf[ks])[0]); }
-            else mfma_a(acc_o[dt0 + u], vfr[bi % NVB][u], pf[ks]);
-            if (HSTU_PC_DSPREAD != 0 && bi < HSTU_PC_DSPREAD && (u & 1)) {   // behind every second MFMA of the first batches: PER K + PER V instructions
-              constexpr int NSLOT = 2 * (HSTU_PC_DSPREAD ? HSTU_PC_DSPREAD : 1), PER = (NO + NSLOT - 1) / NSLOT;
-              const int slot = 2 * bi + (u >> 1);
-              if (spread) {
-#pragma unroll
-                for (int x = PER * slot; x < PER * slot + PER; ++x)
-                  if (x < NO) {
-                    dma16(kb + x * kstep, kvoff[x], kdst + x * (RPI * ROWB * 2));
-                    dma16(vb + x * vstep, vvoff[x], vdst + x * (RPI * ROWB * 2));
-                  }
-              }
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      TICK(t7);
-      TACC(5, t6, t7);
-#if HSTU_TIMING
-      tsum[6] += 1;
-#endif
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (no DMA may be in flight into LDS when the block retires)
-#if HSTU_TIMING
-  t_dump();
-#endif
-  {
-    fence_a_2w(acc_o);
-    if (qloc < Lq) {
-      uint16_t* op = a.out + (int64_t)(s.start + qloc) * a.o_row + (int64_t)h * a.o_head;
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          uint2 o;
-          o.x = pack_bf16(acc_o[dt][4 * g4 + 0], acc_o[dt][4 * g4 + 1]);
-          o.y = pack_bf16(acc_o[dt][4 * g4 + 2], acc_o[dt][4 * g4 + 3]);
-          *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g4 + 4 * hi) = o;
-        }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The S-wave / O-wave forward over PAIRS of row blocks (round 4; the default at head dim 256): one workgroup takes the z-th
-// heaviest and the z-th lightest row block of a (sequence, head) column and runs them as ONE tile stream -- block A's key
-// tiles, then block B's -- through the same rings.  Under a causal mask every pair carries the same number of key tiles
-// (C3: 8 + 2 and 6 + 4 of a column's four blocks; 32 x 4096: 33 each), so the grid is balanced by construction and, at C3,
-// exactly one workgroup per CU; the second block's first K tile is prefetched under the first block's last tile, the O waves
-// store block A's rows while the S waves already work on block B's first tile, and the pipeline fills and drains once per
-// pair instead of once per block.  Same tiles, same MFMA order, same roundings as hstu_fwd_pc_kernel: bit-identical output.
-// ---------------------------------------------------------------------------------------------------
-template <int D, bool kWin>
-__global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
-  static_assert(D == 256, "rows of 32 chunks");
-  constexpr int CPR = D / 8, RPI = 64 / CPR, ROWB = D, TENS = kBN * ROWB, NINS = kBN / RPI;
-  extern __shared__ __attribute__((aligned(16))) uint16_t smem[];   // [K 0 | K 1 | V 0 | V 1 | P 0 | P 1]
-  uint16_t* const Kring = smem;
-  uint16_t* const Vring = smem + 2 * TENS;
-  uint16_t* const Pring = smem + 4 * TENS;
-
-  const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, ceil(blocks / 2)): z = the pair's rank inside its column
-  const int b = bs.b, h = bs.h;
-  SeqInfo s;
-  s.start = bs.start;
-  const int Lq = bs.end - s.start;
-  const int kstart = a.cu_seqlens_k ? a.cu_seqlens_k[b] : s.start;
-  s.L = a.cu_seqlens_k ? a.cu_seqlens_k[b + 1] - kstart : Lq;
-  const int dq = s.L - Lq;
-  const int nblk = (Lq + kBM - 1) / kBM;
-  if (2 * bs.z >= nblk || dq < 0) return;
-  const int rank0 = bs.z, rank1 = nblk - 1 - bs.z;
-  const bool two = rank1 > rank0;
-  s.has_ctx = a.num_contexts != nullptr;
-  s.has_tgt = a.num_targets != nullptr;
-  s.c = s.has_ctx ? a.num_contexts[b] : 0;
-  s.hlen = s.L - (s.has_tgt ? a.num_targets[b] : 0);
-  s.wl = kWin ? a.wl : -1; s.wr = kWin ? a.wr : -1;
-
-  const int lane = lane_id(), hi = lane >> 5, l31 = lane & 31;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int role = wv >> 2, pw = wv & 3;
   // ---- one row block of the pair
   struct Blk { int m0, qrow0, qloc, n_beg, w_beg, w_end, T; bool wave_live; RowMask rm; };
   auto setup = [&](int rank) -> Blk {
@@ -1515,7 +987,12 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
   const int T0 = B0.T, T1 = two ? B1.T : 0, N = T0 + T1;     // items of the tile stream: block A's tiles, then block B's
   auto item_n0 = [&](int i) { return i < T0 ? B0.n_beg + kBN * i : B1.n_beg + kBN * (i - T0); };
 
-  // ---- LDS-DMA (as hstu_fwd_pc_kernel; the O waves issue everything)
+  // ---- the DMA of one tile of one tensor, issued by the O waves: instruction j moves rows 2 j, 2 j + 1, O wave pw issues
+  // [NO pw, NO pw + NO).  Lane -> (row inside the instruction, LDS chunk slot p); the lane fetches global chunk p ^ swizzle(row).
+  // Addressing: a wave-uniform 64-bit row base (SGPR arithmetic) plus a per-lane 32-bit offset that depends on the instruction
+  // only through j mod 8 -- NO registers per tensor computed once (64-bit per-lane pointers per instruction cost 2 multiplies and
+  // a spilled pointer each, and the reload's vmcnt(0) serialised the DMAs).  Rows past the sequence end (the sequence's last
+  // tile only) are read clamped: their P is zero.
   const uint16_t* kg = a.k + (int64_t)kstart * a.k_row + (int64_t)h * a.k_head;
   const uint16_t* vg = a.v + (int64_t)kstart * a.v_row + (int64_t)h * a.v_head;
   const int dma_r = lane / CPR, dma_p = lane % CPR;
@@ -1528,6 +1005,9 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
     kvoff[u] = (uint32_t)dma_r * (uint32_t)a.k_row * 2u + 16u * (uint32_t)(dma_p ^ (r & 15));
     vvoff[u] = (uint32_t)dma_r * (uint32_t)a.v_row * 2u + 16u * (uint32_t)(dma_p ^ ((r & 3) << 2));
   }
+  // The DMA instruction is issued from inline asm: hipcc models the builtin as an LDS store in flight and puts a vmcnt(0) in
+  // front of the next transpose read of ANY LDS address (seen in the removed one-kind DMA forward's GEMM 2: the prefetch it was
+  // meant to overlap is drained first).  Here the completion is counted by hand: vmcnt(0) + barrier at the loop head.
   auto dma16 = [&](const char* sbase, uint32_t voff, uint32_t lds_byte) {
     uint32_t keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
@@ -1568,6 +1048,22 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
     return __builtin_bit_cast(bf16x8_t, r);
   };
 
+  // Two loops, one per role, with the same trip count and ONE barrier per iteration each (a single loop with the role
+  // test inside keeps Q and the O accumulator live together: 192 registers before anything else, 363 spilled).
+#if HSTU_TIMING
+  unsigned tsum[7] = {0, 0, 0, 0, 0, 0, 0};   // O: wait for own DMA, barrier, DMA issue, -, -, GEMM 2, tiles | S: -, barrier, -,
+  const unsigned t_start = tick();            // GEMM 1 sub-tile 1 + SiLU 0, GEMM 1 sub-tile 0, SiLU sub-tile 1 + hand-off, tiles
+  auto t_dump = [&]() {
+    const unsigned t_end = tick();
+    if (lane == 0) {
+      const int blk = ((int)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+      unsigned long long* d = g_hstu_dbg + ((size_t)(blk * 8 + wv) % 65536) * 8;
+      for (int i = 0; i < 7; ++i) d[i] = tsum[i];
+      d[6] |= (unsigned long long)role << 32;
+      d[7] = t_end - t_start;
+    }
+  };
+#endif
   if (role == 0) {
     // =========================== S waves: item `it` -> P ring slot it & 1 ===========================
     bf16x8_t qf[D / 16];
@@ -1583,7 +1079,10 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
     // Two loops over ONE stream of iterations (block A's items, then block B's + the draining iteration): with a single loop
     // and the block switch inside it hipcc carried Q / the O accumulator through phis and spilled them.
     auto s_iter = [&](int it) {
+      TICK(t1);
       __syncthreads();                     // (no vmcnt wait here: the S waves issue no DMA)
+      TICK(t2);
+      TACC(1, t1, t2);
       if (it >= N) return;
       const bool second = it >= T0;
       const int t_in = second ? it - T0 : it;
@@ -1598,6 +1097,9 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
       const bool full = a.causal && s.wl < 0 && (n0 + kBN - 1 <= dq + qrow0) && (!s.has_ctx || dq + qrow0 >= s.c) && (!s.has_tgt || n0 + kBN - 1 < s.hlen);
       const int mode = full ? 0 : ((!s.has_ctx && !s.has_tgt && s.wl < 0) ? 1 : 2);
       u32x4_t* pdst = reinterpret_cast<u32x4_t*>(Pring) + (((it & 1) * 4 + pw) * 4) * 64 + lane;
+      TICK(t5);
+      // One tile, software-pipelined inside the wave: GEMM 1 of the second 32-key sub-tile carries the SiLU of the first
+      // (one element pair per two MFMAs), so that only the second sub-tile's SiLU runs without MFMAs of this wave.
       auto tile = [&](auto modec) {
         constexpr int kMode = decltype(modec)::value;
         constexpr int SLB = 4, NBAT = (D / 16) / SLB, NKB = HSTU_PC_KBUF;
@@ -1656,6 +1158,8 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
           mfma_b(gb);
           __builtin_amdgcn_sched_barrier(0);
         }
+        TICK(t6);
+        TACC(4, t5, t6);
         uint32_t pk[8];
 #pragma unroll
         for (int gb = NBAT; gb < 2 * NBAT; ++gb) {
@@ -1667,14 +1171,21 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
           if (bi == 3) pdst[1 * 64] = u32x4_t{pk[4], pk[5], pk[6], pk[7]};
           __builtin_amdgcn_sched_barrier(0);
         }
+        TICK(t6b);
+        TACC(3, t6, t6b);
         group(std::integral_constant<int, 8>{}, 1, 0, pk);
         pdst[2 * 64] = u32x4_t{pk[0], pk[1], pk[2], pk[3]};
         group(std::integral_constant<int, 8>{}, 1, 8, pk + 4);
         pdst[3 * 64] = u32x4_t{pk[4], pk[5], pk[6], pk[7]};
+        TICK(t7);
+        TACC(5, t6b, t7);
       };
       if (mode == 0) tile(std::integral_constant<int, 0>{});
       else if (mode == 1) tile(std::integral_constant<int, 1>{});
       else tile(std::integral_constant<int, 2>{});
+#if HSTU_TIMING
+      tsum[6] += 1;
+#endif
     };
     // (block B's queries are loaded at the switch, while the O waves finish block A's last tile and store its rows.  Fetched
     // at kernel entry next to block A's -- hipcc parks them in scratch -- the prologue burst of all CUs doubles: C3 39.3 ->
@@ -1683,6 +1194,9 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
     for (int it = 0; it < T0; ++it) s_iter(it);
     if (two) load_q(B1);
     for (int it = T0; it <= N; ++it) s_iter(it);
+#if HSTU_TIMING
+    t_dump();
+#endif
     return;
   }
   // =========================== O waves: item `it - 1`; DMA of K item it + 1 and V item it ===========================
@@ -1694,7 +1208,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
       for (int r = 0; r < 16; ++r) acc_o[dt][r] = 0.f;
   };
   auto store_rows = [&](int qloc) {
-    fence_a_2w(acc_o);
     if (qloc < Lq) {
       uint16_t* op = a.out + (int64_t)(s.start + qloc) * a.o_row + (int64_t)h * a.o_head;
 #pragma unroll
@@ -1711,12 +1224,15 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
   zero_acc();
   if (N > 0) issue_dma(kg, a.k_row, kvoff, Kring, 0);
   auto o_iter = [&](int it) {
-    pin_agpr_2w(acc_o);
+    TICK(t0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces (K item it, V item it - 1) have landed ...
+    TICK(t1);
     __syncthreads();                                    // ... everyone's have, P[it - 1] is written, the other buffers are free
+    TICK(t2);
     if (it + 1 < N) issue_dma(kg, a.k_row, kvoff, Kring, it + 1);
     if (it < N) issue_dma(vg, a.v_row, vvoff, Vring, it);
-    pin_agpr_2w(acc_o);
+    TICK(t3);
+    TACC(0, t0, t1); TACC(1, t1, t2); TACC(2, t2, t3);
     const int tl = it - 1;
     if (tl >= 0) {
       const bool second = tl >= T0;
@@ -1724,6 +1240,7 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
       const int n0 = (second ? B1.n_beg : B0.n_beg) + kBN * t_in;
       const bool live = (second ? B1.wave_live : B0.wave_live) && n0 < (second ? B1.w_end : B0.w_end) && n0 >= (second ? B1.w_beg : B0.w_beg);
       if (live) {
+        TICK(t6);
         const uint16_t* Vt = Vring + (tl & 1) * TENS;
         const u32x4_t* psrc = reinterpret_cast<const u32x4_t*>(Pring) + (((tl & 1) * 4 + pw) * 4) * 64 + lane;
         bf16x8_t pf[4];
@@ -1739,7 +1256,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
         };
 #pragma unroll
         for (int bi = 0; bi < NVB - 1; ++bi) load_v(bi);
-        pin_agpr_2w(acc_o);
 #pragma unroll
         for (int bi = 0; bi < NBAT2; ++bi) {
           const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
@@ -1749,6 +1265,11 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
           for (int u = 0; u < DB; ++u) mfma_a(acc_o[dt0 + u], vfr[bi % NVB][u], pf[ks]);
           __builtin_amdgcn_sched_barrier(0);
         }
+        TICK(t7);
+        TACC(5, t6, t7);
+#if HSTU_TIMING
+        tsum[6] += 1;
+#endif
       }
     }
   };
@@ -1760,13 +1281,16 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
     for (int it = T0 + 1; it <= N; ++it) o_iter(it);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (no DMA may be in flight into LDS when the block retires)
+#if HSTU_TIMING
+  t_dump();
+#endif
   store_rows(two ? B1.qloc : B0.qloc);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // The S-wave / O-wave forward with TWO MFMAs per LDS fragment (round 4; the default at head dim 256).
 // tools/ubench_mfma.hip: the matrix pipe issues a 32x32x16 MFMA every 32 clocks whatever the partner wave does -- but in
-// hstu_fwd_pc_kernel / hstu_fwd_pair_kernel every MFMA consumes a fresh 1 KB fragment from LDS (each wave owns 32 query rows),
+// hstu_fwd_pair_kernel every MFMA consumes a fresh 1 KB fragment from LDS (each wave owns 32 query rows),
 // 4 SIMDs x 1 KB / 32 clk = the CU's whole 128 B/clk of LDS bandwidth before the DMA writes and the P hand-off: 352 KB per
 // 64-key tile, ~4 000 clocks per tile measured = 88 B/clk.  They are LDS-bound; that is the "45-52 clocks per MFMA" of their stamps.
 // Here a wave owns 64 query rows, so that every K and every V^T fragment read feeds two MFMAs:
@@ -1776,16 +1300,13 @@ __global__ void __launch_bounds__(512) hstu_fwd_pair_kernel(AttnArgs a) {
 //                        (8 KB) and 16 V^T fragments (16 KB), 32 MFMAs; issues the tile's LDS-DMA as before.
 // LDS traffic per tile: K 64 + V 64 + P 16 written / 32 read + DMA 64 = 240 KB (352 before).  Rings, swizzles, the one barrier
 // per tile, the lag of one tile between the roles and the optional (heavy, light) pairing of row blocks (kPair) are those of
-// the two kernels above; same MFMA order per output element, same roundings: bit-identical output.
+// the kernel above; same MFMA order per output element, same roundings: bit-identical output.
 // Measured and rejected: the S waves software-pipelined across tiles (GEMM 1 of tile t between the SiLU groups of tile t - 1, the
 // O waves two tiles behind): Q (128) + two accumulator sets (64) + fragments do not fit 256 registers -- hipcc spills 45 of them and
 // reloads Q fragments from scratch inside the loop: 708-745 TFLOP/s against 866-948 at L = 4096 (same bits).
 // ---------------------------------------------------------------------------------------------------
 #ifndef HSTU_Q2_KBUF
 #define HSTU_Q2_KBUF 3   // S waves: K fragment batches (2 slices = 4 MFMAs) in registers, KBUF - 1 in flight
-#endif
-#ifndef HSTU_Q2_PK
-#define HSTU_Q2_PK 0   // S waves: SiLU's plain VALU work as packed fp32 pairs
 #endif
 #ifndef HSTU_Q2_VBUF
 #define HSTU_Q2_VBUF 3   // O waves: V^T fragment batches (2 fragments = 4 MFMAs) likewise
@@ -2028,27 +1549,11 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
         }
         TICK(t6);
         TACC(4, t5, t6);
-        // SiLU, mask, 1 / N, pack: elements r0 .. r0 + 7 of q tile qt -> one key slice (4 packed words), stage by stage
+        // SiLU, mask, 1 / N, pack: elements r0 .. r0 + 7 of q tile qt -> one key slice (4 packed words), stage by stage (measured
+        // and rejected: the plain multiplies and the add as packed fp32 pairs, v_pk_mul_f32 / v_pk_add_f32)
         auto group = [&](int qt, int r0, uint32_t* out) {
           constexpr int NE = 8;
           float y[NE];
-#if HSTU_Q2_PK
-          {   // the plain multiplies and the add as packed fp32 pairs (v_pk_mul_f32 / v_pk_add_f32): same operations, same roundings
-            f32x2_t x2[NE / 2], e2[NE / 2];
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) x2[i] = f32x2_t{acc_s[qt][r0 + 2 * i], acc_s[qt][r0 + 2 * i + 1]};
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) e2[i] = x2[i] * nal2e;
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) e2[i] = f32x2_t{__builtin_amdgcn_exp2f(e2[i].x), __builtin_amdgcn_exp2f(e2[i].y)};
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) e2[i] = e2[i] + 1.0f;
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) e2[i] = f32x2_t{__builtin_amdgcn_rcpf(e2[i].x), __builtin_amdgcn_rcpf(e2[i].y)};
-#pragma unroll
-            for (int i = 0; i < NE / 2; ++i) { const f32x2_t t = x2[i] * ais * e2[i]; y[2 * i] = t.x; y[2 * i + 1] = t.y; }
-          }
-#else
           float x[NE], e[NE];
 #pragma unroll
           for (int i = 0; i < NE; ++i) x[i] = acc_s[qt][r0 + i];
@@ -2062,7 +1567,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
           for (int i = 0; i < NE; ++i) e[i] = __builtin_amdgcn_rcpf(e[i]);
 #pragma unroll
           for (int i = 0; i < NE; ++i) y[i] = x[i] * ais * e[i];
-#endif
           if (kMode != 0) {
             const int th = rm[qt].jmax - k0 - 4 * hi;     // kMode 1: element rr is visible iff (rr & 3) + 8 (rr >> 2) <= th
             const int kb = k0 + 4 * hi;                   // kMode 3: the general rule and the row's functions
@@ -2180,7 +1684,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
       for (int r = 0; r < 16; ++r) acc_o[t][r] = 0.f;
   };
   auto store_rows = [&](const Blk& k) {
-    fence_a_2w(acc_o);
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const int qloc = k.hrow0 + 32 * qt + l31;
@@ -2201,7 +1704,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
   zero_acc();
   if (N > 0) issue_dma(kg, a.k_row, kvoff, Kring, 0);
   auto o_iter = [&](int it, const Blk& k, int t_in) {     // k, t_in: the block and tile of item it - 1 (t_in < 0: none)
-    pin_agpr_2w(acc_o);
     TICK(t0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces (K item it, V item it - 1) have landed ...
     TICK(t1);
@@ -2209,7 +1711,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
     TICK(t2);
     if (it + 1 < N) issue_dma(kg, a.k_row, kvoff, Kring, it + 1);
     if (it < N) issue_dma(vg, a.v_row, vvoff, Vring, it);
-    pin_agpr_2w(acc_o);
     TICK(t3);
     TACC(0, t0, t1); TACC(1, t1, t2); TACC(2, t2, t3);
     const int tl = it - 1;
@@ -2231,7 +1732,6 @@ __global__ void __launch_bounds__(512) hstu_fwd_q2_kernel(AttnArgs a) {
         };
 #pragma unroll
         for (int bi = 0; bi < NVB - 1; ++bi) load_v(bi);
-        pin_agpr_2w(acc_o);
 #pragma unroll
         for (int bi = 0; bi < NBAT2; ++bi) {
           const int ks = bi / (4 / DB), dtl0 = (bi % (4 / DB)) * DB;
@@ -2334,7 +1834,8 @@ struct RowTile {
       if (NCH % 256 == 0 || ch < NCH) *reinterpret_cast<u32x4_t*>(dst + (ch / (D / 8)) * (D + 8) + 8 * (ch % (D / 8))) = v;
     }
   }
-  // the same rows once more with the transpose-read stride (tr_frag): the image a TransTile would have transposed
+  // the same rows once more with the transpose-read stride (tr_frag): the image a transposed [D][NR] copy would hold, read
+  // through the hardware transpose instead
   __device__ __forceinline__ void commit_tr(uint16_t* dst, int row0, int L) const {
 #pragma unroll
     for (int i = 0; i < PT; ++i) {
@@ -2345,71 +1846,6 @@ struct RowTile {
     }
   }
 };
-// TransTile: the same rows transposed -> LDS [D][NR+8], row positions permuted inside every 16-group
-// ({0-3,8-11,4-7,12-15}) so that an MFMA accumulator's register order is directly the k order of the next GEMM.
-template <int D, int NR>
-struct TransTile {
-  static constexpr int NCH = (NR / 4) * (D / 8), PT = (NCH + 255) / 256;
-  u32x4_t r[PT][4];
-  __device__ __forceinline__ void fetch(const uint16_t* src, int64_t row_stride, int row0, int L) {
-    if constexpr (NCH % 256 == 0) {
-      if (row0 + NR <= L) {   // tile inside the sequence (uniform): four row pointers per thread, immediate column offsets
-        const int gpos = (int)threadIdx.x % (NR / 4), g16 = gpos >> 2, pg = gpos & 3;
-        const int ak = pg == 1 ? 2 : (pg == 2 ? 1 : pg);
-        const uint16_t* p = src + (int64_t)(row0 + 16 * g16 + 4 * ak) * row_stride + 8 * ((int)threadIdx.x / (NR / 4));
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-          for (int i = 0; i < PT; ++i) r[i][kk] = *reinterpret_cast<const u32x4_t*>(p + 8 * (256 / (NR / 4)) * i);
-          p += row_stride;
-        }
-        return;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      const int ch = (threadIdx.x + 256 * i) % NCH;   // threads past NCH repeat a block (their writes are skipped)
-      const int gpos = ch % (NR / 4), dc = ch / (NR / 4);
-      const int g16 = gpos >> 2, pg = gpos & 3;
-      const int ak = pg == 1 ? 2 : (pg == 2 ? 1 : pg);
-      const int r0 = row0 + 16 * g16 + 4 * ak;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const int row = r0 + kk;
-        r[i][kk] = *reinterpret_cast<const u32x4_t*>(src + (int64_t)(row < L ? row : L - 1) * row_stride + 8 * dc);
-      }
-    }
-  }
-  __device__ __forceinline__ void commit(uint16_t* dst, int row0, int L) const {
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      const int ch = threadIdx.x + 256 * i;
-      if (NCH % 256 != 0 && ch >= NCH) continue;
-      const int gpos = ch % (NR / 4), dc = ch / (NR / 4);
-      const int g16 = gpos >> 2, pg = gpos & 3;
-      const int ak = pg == 1 ? 2 : (pg == 2 ? 1 : pg);
-      const int r0 = row0 + 16 * g16 + 4 * ak;
-      const u32x4_t z = {0u, 0u, 0u, 0u};
-      const u32x4_t w0 = r0 + 0 < L ? r[i][0] : z, w1 = r0 + 1 < L ? r[i][1] : z, w2 = r0 + 2 < L ? r[i][2] : z,
-                    w3 = r0 + 3 < L ? r[i][3] : z;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const uint32_t sel = (e & 1) ? 0x07060302u : 0x05040100u;
-        uint2 o;
-        o.x = __builtin_amdgcn_perm(w1[e >> 1], w0[e >> 1], sel);
-        o.y = __builtin_amdgcn_perm(w3[e >> 1], w2[e >> 1], sel);
-        *reinterpret_cast<uint2*>(dst + (8 * dc + e) * (NR + 8) + 16 * g16 + 4 * pg) = o;
-      }
-    }
-  }
-};
-struct NoTile {
-  __device__ __forceinline__ void fetch(const uint16_t*, int64_t, int, int) {}
-  __device__ __forceinline__ void commit(uint16_t*, int, int) const {}
-  __device__ __forceinline__ void commit_tr(uint16_t*, int, int) const {}
-};
-template <bool C, typename A, typename B> struct SelT { typedef A type; };
-template <typename A, typename B> struct SelT<false, A, B> { typedef B type; };
 
 // B-operand fragments of the wave's own 32 rows (lane = row l31, 8 consecutive d per 16-slice); clamped rows
 template <int D>
@@ -2683,15 +2119,14 @@ template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = fals
 __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;   // kXP (MODE 2): P is computed as well and left for the dV pass
-  constexpr int RS = D + 8, TS = BQ + 8, NT = BQ / 32;
-  constexpr bool kTR = HSTU_BWD_TR != 0;            // Q^T / dO^T operands by transpose reads from row-major images
-  constexpr int TRS = TrStride<D>::value;
-  constexpr int TIMG = kTR ? BQ * TRS : D * TS;     // elements of one "transposed" image
+  constexpr int RS = D + 8, NT = BQ / 32;
+  constexpr int TRS = TrStride<D>::value;           // Q^T / dO^T operands by transpose reads from row-major images
+  constexpr int TIMG = BQ * TRS;                    // elements of one "transposed" image
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   uint16_t* Qs = smem;                              // [BQ][RS]   (S)
   uint16_t* dOs = Qs + BQ * RS;                     // [BQ][RS]   (dP; kDK only)
-  uint16_t* Qt = dOs + (kDK ? BQ * RS : 0);         // [D][TS] or [BQ][TRS]   (dK; kDK only)
-  uint16_t* dOt = Qt + (kDK ? TIMG : 0);            // [D][TS] or [BQ][TRS]   (dV; kDV only)
+  uint16_t* Qt = dOs + (kDK ? BQ * RS : 0);         // [BQ][TRS]  (dK; kDK only)
+  uint16_t* dOt = Qt + (kDK ? TIMG : 0);            // [BQ][TRS]  (dV; kDV only)
 
   const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks): see launch_fwd
   const int b = bs.b, h = bs.h;
@@ -2755,17 +2190,12 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   auto advance = [&](int i) { i += BQ; return (i >= c_end && i < jump) ? jump : i; };
   int i0 = c_end > 0 ? 0 : jump;
 
-  // kTR: the "transposed" images are second row-major copies of the SAME fetched registers (no second global read,
-  // no perm network); only MODE 1, which has no other use for dO rows, fetches dO for that image alone
-  typename SelT<true, RowTile<D, BQ>, NoTile>::type q_rows;
-  typename SelT<kDK || (kTR && kDV), RowTile<D, BQ>, NoTile>::type do_rows;
-  typename SelT<kDK && !kTR, TransTile<D, BQ>, NoTile>::type q_tr;
-  typename SelT<kDV && !kTR, TransTile<D, BQ>, NoTile>::type do_tr;
+  // the "transposed" images are second row-major copies of the SAME fetched registers (no second global read, no perm
+  // network); only MODE 1, which has no other use for dO rows, fetches dO for that image alone
+  RowTile<D, BQ> q_rows, do_rows;
   auto fetch_all = [&](int i) {
     q_rows.fetch(qbase, a.q_row, i, s.L);
     do_rows.fetch(dobase, g.do_row, i, s.L);
-    q_tr.fetch(qbase, a.q_row, i, s.L);
-    do_tr.fetch(dobase, g.do_row, i, s.L);
   };
   // kPre: small head dims run several waves per SIMD, which hides the staging latency better than holding a tile in
   // registers does (the prefetch registers would halve the occupancy); d = 256 runs one wave per SIMD and prefetches
@@ -2784,13 +2214,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
     TICK(t1b);
     q_rows.commit(Qs, i0, s.L);
     if (kDK) do_rows.commit(dOs, i0, s.L);
-    if constexpr (kTR) {
-      if (kDK) q_rows.commit_tr(Qt, i0, s.L);
-      if (kDV) do_rows.commit_tr(dOt, i0, s.L);
-    } else {
-      q_tr.commit(Qt, i0, s.L);
-      do_tr.commit(dOt, i0, s.L);
-    }
+    if (kDK) q_rows.commit_tr(Qt, i0, s.L);
+    if (kDV) do_rows.commit_tr(dOt, i0, s.L);
     if (kDV) pin_agpr(acc_dv);
     if (kDK) pin_agpr(acc_dk);
     TICK(t2);
@@ -2975,14 +2400,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
         const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
 #pragma unroll
         for (int u = 0; u < DB; ++u) {
-          if constexpr (kTR) {
-            if (kDV) fa[buf][u] = tr_frag<TRS>(dOt, dt0 + u, ks, lane, hi);
-            if (kDK) fb[buf][u] = tr_frag<TRS>(Qt, dt0 + u, ks, lane, hi);
-          } else {
-            const int off = (32 * (dt0 + u) + l31) * TS + 16 * ks + 8 * hi;
-            if (kDV) fa[buf][u] = *reinterpret_cast<const bf16x8_t*>(dOt + off);
-            if (kDK) fb[buf][u] = *reinterpret_cast<const bf16x8_t*>(Qt + off);
-          }
+          if (kDV) fa[buf][u] = tr_frag<TRS>(dOt, dt0 + u, ks, lane, hi);
+          if (kDK) fb[buf][u] = tr_frag<TRS>(Qt, dt0 + u, ks, lane, hi);
         }
       };
       load_t(0, 0);
@@ -3039,13 +2458,12 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
 template <int D, int BK, bool kPre, bool kRab = false>
 __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
-  constexpr int RS = D + 8, TS = BK + 8, NT = BK / 32;
-  constexpr bool kTR = HSTU_BWD_TR != 0;   // K^T operand of the dQ GEMM by transpose reads from a row-major image
-  constexpr int TRS = TrStride<D>::value;
+  constexpr int RS = D + 8, NT = BK / 32;
+  constexpr int TRS = TrStride<D>::value;   // K^T operand of the dQ GEMM by transpose reads from a row-major image
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   uint16_t* Ks = smem;               // [BK][RS]
   uint16_t* Vs = Ks + BK * RS;       // [BK][RS]
-  uint16_t* Kt = Vs + BK * RS;       // [D][TS] or [BK][TRS]
+  uint16_t* Kt = Vs + BK * RS;       // [BK][TRS]
 
   const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks): see launch_fwd
   const int b = bs.b, h = bs.h;
@@ -3103,11 +2521,9 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   const uint16_t* kbase = a.k + (int64_t)s.start * a.k_row + (int64_t)h * a.k_head;
   const uint16_t* vbase = a.v + (int64_t)s.start * a.v_row + (int64_t)h * a.v_head;
   RowTile<D, BK> k_rows, v_rows;
-  typename SelT<!kTR, TransTile<D, BK>, NoTile>::type k_tr;
   auto fetch_all = [&](int n) {
     k_rows.fetch(kbase, a.k_row, n, s.L);
     v_rows.fetch(vbase, a.v_row, n, s.L);
-    k_tr.fetch(kbase, a.k_row, n, s.L);
   };
   if (kPre && n_end > n_beg) fetch_all(n_beg);
   for (int n0 = n_beg; n0 < n_end; n0 += BK) {
@@ -3116,7 +2532,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
     if (!kPre) fetch_all(n0);
     k_rows.commit(Ks, n0, s.L);
     v_rows.commit(Vs, n0, s.L);
-    if constexpr (kTR) k_rows.commit_tr(Kt, n0, s.L); else k_tr.commit(Kt, n0, s.L);
+    k_rows.commit_tr(Kt, n0, s.L);
     pin_agpr(acc_dq);
     __syncthreads();
     if (kPre && n0 + BK < n_end) fetch_all(n0 + BK);
@@ -3193,9 +2609,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
       auto load_t = [&](int bi, int buf) {
         const int ks = bi / (NDT / DB), dt0 = (bi % (NDT / DB)) * DB;
 #pragma unroll
-        for (int u = 0; u < DB; ++u)
-          if constexpr (kTR) fk[buf][u] = tr_frag<TRS>(Kt, dt0 + u, ks, lane, hi);
-          else fk[buf][u] = *reinterpret_cast<const bf16x8_t*>(Kt + (32 * (dt0 + u) + l31) * TS + 16 * ks + 8 * hi);
+        for (int u = 0; u < DB; ++u) fk[buf][u] = tr_frag<TRS>(Kt, dt0 + u, ks, lane, hi);
       };
       load_t(0, 0);
 #pragma unroll
@@ -3476,28 +2890,20 @@ __global__ void __launch_bounds__(256, HSTU_XOCC) hstu_bwd_v_p_kernel(BwdAttnArg
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The one-GEMM passes of the exchange with EIGHT waves (round 4, head dim 256): one workgroup owns 256 keys (dV from P) or
-// 256 query rows (dQ from dS), 32 per wave, two waves per SIMD (128 accumulator registers + < 128 others each), and streams
-// the other side's rows -- dO resp. K -- in 64-row tiles that go global -> LDS by LDS-DMA (inline asm: see
-// hstu_fwd_pc_kernel), double-buffered, one barrier per step, read back transposed under the forward's V swizzle.  Against
-// the 4-wave kernels: the staged tile feeds twice the MFMAs (half the L2 -> LDS bytes per FLOP: those passes moved 13 B per
+// The one-GEMM passes of the exchange with DMA-staged tiles (round 4, head dim 256): one 4-wave workgroup owns 128 keys (dV
+// from P) or 128 query rows (dQ from dS), 32 per wave, two workgroups per CU -- two waves per SIMD (128 accumulator registers
+// + < 128 others each) -- and streams the other side's rows -- dO resp. K -- in 64-row tiles that go global -> LDS by LDS-DMA
+// (inline asm: see hstu_fwd_pair_kernel), double-buffered, one barrier per step, read back transposed under the forward's V
+// swizzle.  Against the register-staged kernels: the staged tile feeds more MFMAs per LDS byte (those passes moved 13 B per
 // clock and CU, what L2 + HBM deliver), no staging registers, no commit phase, and a second wave per SIMD to cover the P / dS
-// loads and the fragment reads.
+// loads and the fragment reads.  Measured and rejected: one 8-wave workgroup of 256 rows per CU (causal work balances worse
+// over the CUs: a chunk of the capped exchange may hold only one 256-row block per CU).
 // ---------------------------------------------------------------------------------------------------
-#ifndef HSTU_KVPC_MIDBAR
-#define HSTU_KVPC_MIDBAR 0   // 1 = a second barrier per step: the S waves arrive after their GEMMs, the K waves after their DMA issue, so the dK GEMM runs under the elementwise phase
-#endif
-#ifndef HSTU_KVPC_PROBE
-#define HSTU_KVPC_PROBE 0   // timing probe (wrong results): 1 = the S waves' GEMMs reuse their first fragment batches (no LDS reads)
-#endif
-#ifndef HSTU_KVPC_KSLEEP
-#define HSTU_KVPC_KSLEEP 0   // K waves of the dK pass: s_sleep units (64 cycles each) between the DMA issue and the dK GEMM
-#endif
 #ifndef HSTU_KVPC_FBUF
 #define HSTU_KVPC_FBUF 3   // S waves of the dK pass: Q / dO fragment batches in registers (FBUF - 1 in flight ahead of the MFMAs)
 #endif
 #ifndef HSTU_X8_VBUF
-#define HSTU_X8_VBUF 2   // fragment batches (4 slices) in registers in the 8-wave passes (3 spills at 128 + 128 registers)
+#define HSTU_X8_VBUF 2   // fragment batches (4 slices) in registers in the one-GEMM passes (3 spills at 128 + 128 registers)
 #endif
 template <int NW>
 struct Dma64T {   // LDS-DMA of one 64-row x 256-column bf16 tile by NW waves: 32 instructions of 2 rows, 32 / NW per wave
@@ -3571,10 +2977,10 @@ __device__ __forceinline__ void gemm_x8(f32x16_t (&acc)[8], const uint16_t* ring
   for (int bi = 0; bi < NVB - 1; ++bi) load(bi);
 #pragma unroll
   for (int bi = 0; bi < NB; ++bi) {
-    if (bi + NVB - 1 < NB && !(HSTU_X8_PROBE & 1)) load(bi + NVB - 1);
+    if (bi + NVB - 1 < NB) load(bi + NVB - 1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) mfma_a(acc[4 * (bi & 1) + u], fr[(HSTU_X8_PROBE & 1) ? 0 : bi % NVB][u], bf[bi >> 1]);
+    for (int u = 0; u < 4; ++u) mfma_a(acc[4 * (bi & 1) + u], fr[bi % NVB][u], bf[bi >> 1]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -3591,11 +2997,12 @@ __device__ __forceinline__ void store_acc_rows(const f32x16_t (&acc)[D / 32], ui
     }
 }
 
-// dV from the stored P, 256 keys per workgroup.  The query steps are the union of what the dK pass ran for the block's two
-// 128-key halves (its blocks are kBM keys); a wave consults the span of ITS half to tell which sub-tiles exist.
-template <int D, int NW, bool kFunc = false>
+constexpr int kNW8 = 4;   // waves per workgroup of the one-GEMM passes
+
+// dV from the stored P, 128 keys per workgroup: the query steps of the dK pass's block of the same keys (kBM of them).
+template <int D, bool kFunc = false>
 __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigned bz, unsigned nz) {
-  constexpr int kBM8 = 32 * NW;   // keys per workgroup
+  constexpr int NW = kNW8, kBM8 = 32 * NW;   // keys per workgroup
   static_assert(D == 256, "DMA rows of 32 chunks");
   const AttnArgs& a = g.f;
   constexpr int BQ = 64, NT = 2, TILE = BQ * D;
@@ -3623,17 +3030,15 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
   for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
-  KvSpan sp0 = kv_span(a, s, n0, g.bq_kv);
-  if constexpr (kFunc) { static_assert(NW == 4, "one key block of the dK pass per workgroup"); sp0 = kv_span_clip(sp0, func_kvis_of(g, s.start, b, h, n0), g.bq_kv); }
-  const KvSpan sp1 = (NW == 8 && n0 + kBM < s.L) ? kv_span(a, s, n0 + kBM, g.bq_kv) : sp0;
-  const KvSpan mine = wv < 4 ? sp0 : sp1;
-  const int jump = sp0.jump < sp1.jump ? sp0.jump : sp1.jump, c_end = sp0.c_end > sp1.c_end ? sp0.c_end : sp1.c_end;
-  const int lim = sp0.lim > sp1.lim ? sp0.lim : sp1.lim;
+  static_assert(kBM8 == kBM, "one key block of the dK pass per workgroup");
+  KvSpan sp = kv_span(a, s, n0, g.bq_kv);
+  if constexpr (kFunc) sp = kv_span_clip(sp, func_kvis_of(g, s.start, b, h, n0), g.bq_kv);
+  const int jump = sp.jump, c_end = sp.c_end, lim = sp.lim;
   const int jump_s = (jump / BQ) * BQ, cend_s = ((c_end + BQ - 1) / BQ) * BQ;
   int i_lim = ((lim + g.bq_kv - 1) / g.bq_kv) * g.bq_kv;
   if (i_lim > s.L) i_lim = s.L;
   auto advance = [&](int i) { i += BQ; return (i >= cend_s && i < jump_s) ? jump_s : i; };
-  auto visited = [&](int i) { return i < s.L && kv_visited(mine, (i / g.bq_kv) * g.bq_kv); };
+  auto visited = [&](int i) { return i < s.L && kv_visited(sp, (i / g.bq_kv) * g.bq_kv); };
   Dma64T<NW> dma;
   dma.init(wv, lane, g.do_row);
   u32x4_t pn0[NT], pn1[NT];
@@ -3641,7 +3046,7 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int it = i + 32 * t;
-      if (!(HSTU_X8_PROBE & 2) && wave_live && visited(it) && !xch_absent(xu, key0 >> 5, it >> 5)) {
+      if (wave_live && visited(it) && !xch_absent(xu, key0 >> 5, it >> 5)) {
         const u32x4_t* tp = reinterpret_cast<const u32x4_t*>(g.p_ws + xch_tile(xu, key0 >> 5, it >> 5)) + 2 * lane;
         pn0[t] = xch_load(tp); pn1[t] = xch_load(tp + 1);
       } else {
@@ -3653,7 +3058,6 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
   if (i0 < i_lim) { dma.issue(dobase, g.do_row, i0, s.L, smem, lane); fetch_p(i0); }
   auto step = [&](auto bufc) {
     constexpr int BUF = decltype(bufc)::value;
-    pin_agpr_2w(acc);
     bf16x8_t pf[2 * NT];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of the step (and its P words) have arrived
 #pragma unroll
@@ -3661,9 +3065,8 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
     __syncthreads();                                    // everyone's have; everyone is done with the other buffer
     {
       const int nx = advance(i0);
-      if (nx < i_lim) { if (!(HSTU_X8_PROBE & 4)) dma.issue(dobase, g.do_row, nx, s.L, smem + (BUF ^ 1) * TILE, lane); fetch_p(nx); }
+      if (nx < i_lim) { dma.issue(dobase, g.do_row, nx, s.L, smem + (BUF ^ 1) * TILE, lane); fetch_p(nx); }
     }
-    pin_agpr_2w(acc);
     if (wave_live) gemm_x8<BUF>(acc, smem, pf, lane, hi);
     i0 = advance(i0);
   };
@@ -3672,25 +3075,19 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
     if (i0 >= i_lim) break;
     step(std::integral_constant<int, 1>{});
   }
-  fence_a_2w(acc);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (kj < s.L) store_acc_rows<D>(acc, g.dv + ((int64_t)(s.start + kj) * a.H + h) * D, hi);
 }
 
-// dQ from the stored dS, 256 query rows per workgroup (the layout juggling of hstu_bwd_q_ds_kernel: the 2 KB sub-tile goes
+// dQ from the stored dS, 128 query rows per workgroup (the layout juggling of hstu_bwd_q_ds_kernel: the 2 KB sub-tile goes
 // through a wave-private LDS patch and comes back through transpose reads)
-template <int D, int NW>
-__global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) hstu_bwd_v_p8_kernel(BwdAttnArgs g) {
-  hstu_bwd_v_p8_body<D, NW>(g, blockIdx.z, gridDim.z);
-}
-
-template <int D, int NW, bool kFunc = false>
+template <int D, bool kFunc = false>
 __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsigned bz, unsigned nz) {
-  constexpr int kBM8 = 32 * NW;   // query rows per workgroup
+  constexpr int NW = kNW8, kBM8 = 32 * NW;   // query rows per workgroup
   static_assert(D == 256, "DMA rows of 32 chunks");
   const AttnArgs& a = g.f;
   constexpr int BK = 64, NT = 2, TILE = BK * D;
-  extern __shared__ __attribute__((aligned(16))) uint16_t smem[];   // [2][64][256] K tiles | 8 waves x 2 x 2 KB dS patches
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem[];   // [2][64][256] K tiles | NW waves x 2 x 2 KB dS patches
   const BlockSeq bs = seq_head_of_block(a, bz, nz);
   const int b = bs.b, h = bs.h;
   SeqInfo s;
@@ -3786,7 +3183,7 @@ __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsign
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int nt = n + 32 * t;
-      if (!(HSTU_X8_PROBE & 2) && wave_live && nt < w_end && tile_written(nt) && !xch_absent(xu, nt >> 5, qrow0 >> 5)) {
+      if (wave_live && nt < w_end && tile_written(nt) && !xch_absent(xu, nt >> 5, qrow0 >> 5)) {
         const u32x4_t* tp = reinterpret_cast<const u32x4_t*>(g.ds_ws + xch_tile(xu, nt >> 5, qrow0 >> 5)) + 2 * lane;
         ds0[t] = xch_load(tp); ds1[t] = xch_load(tp + 1);
       } else {
@@ -3798,7 +3195,6 @@ __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsign
   int n0 = n_beg;
   auto step = [&](auto bufc) {
     constexpr int BUF = decltype(bufc)::value;
-    pin_agpr_2w(acc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the wave's dS sub-tiles of this step -> its private patch (read back transposed below; the previous step's reads of the
     // patch are complete: their MFMAs have been issued)
@@ -3808,8 +3204,7 @@ __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsign
       *reinterpret_cast<u32x4_t*>(dSw + 1024 * t + 16 * lane + 8) = ds1[t];
     }
     __syncthreads();
-    { const int nx = next_step(n0); if (nx < n_end) { if (!(HSTU_X8_PROBE & 4)) dma.issue(kbase, a.k_row, nx, s.L, smem + (BUF ^ 1) * TILE, lane); fetch_ds(nx); } }
-    pin_agpr_2w(acc);
+    { const int nx = next_step(n0); if (nx < n_end) { dma.issue(kbase, a.k_row, nx, s.L, smem + (BUF ^ 1) * TILE, lane); fetch_ds(nx); } }
     if (wave_live && n0 < w_end && n0 >= w_beg && !(kFunc && n0 >= wgap_a && n0 < wgap_b)) {
       bf16x8_t sf[2 * NT];
 #pragma unroll
@@ -3831,30 +3226,24 @@ __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsign
     if (n0 >= n_end) break;
     step(std::integral_constant<int, 1>{});
   }
-  fence_a_2w(acc);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (qi < s.L) store_acc_rows<D>(acc, g.dq + ((int64_t)(s.start + qi) * a.H + h) * D, hi);
-}
-
-template <int D, int NW>
-__global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) hstu_bwd_q_ds8_kernel(BwdAttnArgs g) {
-  hstu_bwd_q_ds8_body<D, NW>(g, blockIdx.z, gridDim.z);
 }
 
 // Round 6: the two one-GEMM passes in ONE launch -- they are independent (dV reads P, dQ reads dS, both written by the dK pass) and
 // at C3's 512 rows each is a single generation of blocks whose launch ramp and tail the other can fill: the first half of the
 // block ranks takes the dV role, the second the dQ role (LDS = the larger of the two: 80 KB, two workgroups per CU as before).
-template <int D, int NW, bool kFunc = false>
-__global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) hstu_bwd_vq8_kernel(BwdAttnArgs g) {
+template <int D, bool kFunc = false>
+__global__ void __launch_bounds__(64 * kNW8, 2) hstu_bwd_vq8_kernel(BwdAttnArgs g) {
   const unsigned nz = gridDim.z >> 1;
-  if (blockIdx.z < nz) hstu_bwd_v_p8_body<D, NW, kFunc>(g, blockIdx.z, nz);
-  else hstu_bwd_q_ds8_body<D, NW, kFunc>(g, blockIdx.z - nz, nz);
+  if (blockIdx.z < nz) hstu_bwd_v_p8_body<D, kFunc>(g, blockIdx.z, nz);
+  else hstu_bwd_q_ds8_body<D, kFunc>(g, blockIdx.z - nz, nz);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // What bounds the one-GEMM dV / dQ passes at long sequences (probes of profiles/r04_hstu_bwd_x8_probes.txt, 8 x 4096, one chunk):
-// hstu_bwd_v_p8_kernel 260 us -- 158 without its P loads, 129 without loads and row DMA, 111 without the LDS fragment reads as well
-// (HSTU_X8_PROBE).  The 0.54 GB of P (and of dS) that a pass reads were written by the dK pass and no cache holds them: at the
+// the dV pass 260 us -- 158 without its P loads, 129 without loads and row DMA, 111 without the LDS fragment reads as well
+// (timing probes that dropped those steps).  The 0.54 GB of P (and of dS) that a pass reads were written by the dK pass and no cache holds them: at the
 // ~5.4 TB/s HBM delivers they are 100 us per pass, and 200 us of writes inside the dK pass -- 0.4 of the backward's 1.02 ms.
 // It is bandwidth, not latency: the same passes with the exchange tiles brought in by LDS-DMA TWO steps ahead (one 8-wave
 // workgroup per CU, a three-slot ring of 96 KB next to the row ring, counted vmcnt, bit-identical results) ran 635-642 TFLOP/s
@@ -3869,7 +3258,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) hstu_bwd_vq8_kernel(
 // transpose reads), and issue the LDS-DMA of the step's three images: Q rows and dO rows (K-style swizzle, b128 row reads of
 // the S waves) and Q rows once more under the V-style swizzle (transpose reads of the K waves).  One barrier per step,
 // every ring two deep; the step loop is unrolled by two so that every LDS address is a register plus an immediate.
-// Same MFMA order and roundings as hstu_bwd_kv_kernel<256, 32, 2>: bit-identical dK, P and dS.
+// Same MFMA order and roundings as hstu_bwd_kv_kernel's dK pass in 32-row steps (MODE 2): bit-identical dK, P and dS.
 // Measured and rejected: the S waves in two types -- wave 2 t holds the K fragments of BOTH key tiles of pair t and computes S for
 // 64 keys, wave 2 t + 1 the V fragments and dP, each hands the other tile's accumulator over through LDS behind a second barrier
 // (every Q / dO fragment read then feeds two MFMAs: 64 KB of LDS reads per step instead of 128).  Same time (8 x 4096 backward
@@ -3984,7 +3373,7 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
       const bool have = i0 < i_lim;
       prev_valid = have;
       cur = have ? advance(i0) : i0;
-      if (!have || !wave_live) { if (HSTU_KVPC_MIDBAR) __builtin_amdgcn_s_barrier(); return; }
+      if (!have || !wave_live) return;
       const uint16_t* Qs = Qr + PAR * IMG;
       const uint16_t* Ds = dOr + PAR * IMG;
       f32x16_t acc_s, acc_p;
@@ -4004,7 +3393,7 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
         for (int bi = 0; bi < NFB - 1; ++bi) load_b(bi);
 #pragma unroll
         for (int bi = 0; bi < NBAT; ++bi) {
-          if (bi + NFB - 1 < NBAT && !(HSTU_KVPC_PROBE & 1)) load_b(bi + NFB - 1);
+          if (bi + NFB - 1 < NBAT) load_b(bi + NFB - 1);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int u = 0; u < SLB; ++u) {
@@ -4015,7 +3404,6 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if (HSTU_KVPC_MIDBAR) __builtin_amdgcn_s_barrier();   // (no LDS hazard to order: a pure phase alignment)
       TICK(t2);
       TACC(4, t1, t2);
       const bool tail = i0 + BQ > s.L;     // rows past the sequence are clamped copies here (the 4-wave kernel stages zeros): masked
@@ -4136,7 +3524,6 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
   int cur = first, prev_valid = 0, prev_i = 0;
   auto step = [&](auto parc) {
     constexpr int PAR = decltype(parc)::value;
-    pin_agpr_2w(acc_dk);
     TICK(t0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     commit_func(PAR);                // (the bounds of THIS step's rows, fetched one step ago)
@@ -4159,15 +3546,12 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
     }
     prev_valid = have;
     cur = nxt;
-    pin_agpr_2w(acc_dk);
-    if (HSTU_KVPC_MIDBAR) __builtin_amdgcn_s_barrier();
     TICK(t3);
     TACC(2, t2, t3);
     if (!had || !wave_live) return;
-    // The S waves open a step with 32 MFMAs and close it with ~250 VALU instructions; the K waves' 16 MFMAs belong under the
-    // second half.  Issued straight behind the DMA they fall into the S waves' GEMM (both streams then take turns on the
-    // SIMD's matrix pipe at ~64 cycles per MFMA and the pipe idles through the elementwise phase): park first.
-    if (HSTU_KVPC_KSLEEP) __builtin_amdgcn_s_sleep(HSTU_KVPC_KSLEEP);
+    // The S waves open a step with 32 MFMAs and close it with ~250 VALU instructions, so the K waves' 16 MFMAs issued here fall
+    // into the S waves' GEMM.  Measured and rejected: moving them under the elementwise phase, by s_sleep after the DMA issue or
+    // by a second barrier per step.
     // dK^T[256 x 32 keys] += Q^T[256 x 32 q] dS[32 q x 32 keys] of the PREVIOUS step (rings slot PAR ^ 1)
     const u32x4_t* hp = reinterpret_cast<const u32x4_t*>(Hs) + (((PAR ^ 1) * 4 + pw) * 2) * 64 + lane;
     bf16x8_t sf[2];
@@ -4205,7 +3589,6 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
     if (!(cur < i_lim || prev_valid)) break;
     step(std::integral_constant<int, 1>{});
   }
-  fence_a_2w(acc_dk);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if HSTU_TIMING
   t_dump();
@@ -4216,7 +3599,7 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
 template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false>
 static void launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;
-  const size_t timg = HSTU_BWD_TR ? (size_t)BQ * (D == 32 ? 32 : D + 32) : (size_t)D * (BQ + 8);
+  const size_t timg = (size_t)BQ * TrStride<D>::value;
   const size_t smem = (size_t)(BQ * (D + 8) + (kDK ? BQ * (D + 8) + timg : 0) + (kDV ? timg : 0)) * sizeof(uint16_t);
   static bool attr_set = false;
   if (!attr_set) {
@@ -4227,7 +3610,7 @@ static void launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
 }
 template <int D, int BK, bool kPre, bool kRab = false>
 static void launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
-  const size_t smem_q = (size_t)(2 * BK * (D + 8) + (HSTU_BWD_TR ? (size_t)BK * (D == 32 ? 32 : D + 32) : (size_t)D * (BK + 8))) * sizeof(uint16_t);
+  const size_t smem_q = (size_t)(2 * BK * (D + 8) + BK * TrStride<D>::value) * sizeof(uint16_t);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_q_kernel<D, BK, kPre, kRab>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
@@ -4236,7 +3619,7 @@ static void launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL((hstu_bwd_q_kernel<D, BK, kPre, kRab>), grid, dim3(256), smem_q, stream, g);
 }
 
-template <int D>
+template <int D>   // (head dim 128; 256 takes launch_bwd_x8)
 static void launch_bwd_v_p(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem = (size_t)(HSTU_XSTEP * TrStride<D>::value) * sizeof(uint16_t);
   hipLaunchKernelGGL((hstu_bwd_v_p_kernel<D>), grid, dim3(256), smem, stream, g);
@@ -4248,33 +3631,17 @@ static void launch_bwd_q_ds(const BwdAttnArgs& g, dim3 grid, hipStream_t stream)
   hipLaunchKernelGGL((hstu_bwd_q_ds_kernel<D>), grid, dim3(256), smem, stream, g);
 }
 
-// the DMA-staged one-GEMM passes (head dim 256): MI355_HSTU_X8 = 8: one 8-wave workgroup of 256 rows per CU; 4 (default):
-// 4-wave workgroups of 128 rows, TWO per CU -- the same two waves per SIMD, twice the blocks (causal work balances over the
-// CUs: a chunk of the capped exchange may hold only one 256-row block per CU); 0: the register-staged 4-wave kernels
-template <int NW, bool kFunc = false>
+// the DMA-staged one-GEMM passes (head dim 256): dV and dQ in one launch of 4-wave workgroups, two per CU (hstu_bwd_vq8_kernel)
+template <bool kFunc = false>
 static void launch_bwd_x8(const BwdAttnArgs& g, int B, int max_seqlen, hipStream_t stream) {
-  const size_t smem_v = (size_t)2 * 64 * 256 * sizeof(uint16_t), smem_q = smem_v + (size_t)NW * 2 * 1024 * sizeof(uint16_t);
+  const size_t smem = (size_t)(2 * 64 * 256 + kNW8 * 2 * 1024) * sizeof(uint16_t);   // two dO / K tiles + the dS patches
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_v_p8_kernel<256, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_q_ds8_kernel<256, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_vq8_kernel<256, kFunc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  dim3 grid(g.f.H, B, (max_seqlen + 32 * NW - 1) / (32 * NW));
-#ifndef HSTU_VQ_MERGED
-#define HSTU_VQ_MERGED 1
-#endif
-  if ((HSTU_VQ_MERGED || kFunc) && NW == 4) {
-    static bool attr_m = false;
-    if (!attr_m) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_vq8_kernel<256, NW, kFunc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
-      attr_m = true;
-    }
-    hipLaunchKernelGGL((hstu_bwd_vq8_kernel<256, NW, kFunc>), dim3(grid.x, grid.y, 2 * grid.z), dim3(64 * NW), smem_q, stream, g);
-    return;
-  }
-  hipLaunchKernelGGL((hstu_bwd_v_p8_kernel<256, NW>), grid, dim3(64 * NW), smem_v, stream, g);
-  hipLaunchKernelGGL((hstu_bwd_q_ds8_kernel<256, NW>), grid, dim3(64 * NW), smem_q, stream, g);
+  const int nblk = (max_seqlen + 32 * kNW8 - 1) / (32 * kNW8);
+  hipLaunchKernelGGL((hstu_bwd_vq8_kernel<256, kFunc>), dim3(g.f.H, B, 2 * nblk), dim3(64 * kNW8), smem, stream, g);
 }
 
 template <int D>
@@ -4292,7 +3659,7 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
         attr_pcf = true;
       }
       hipLaunchKernelGGL((hstu_bwd_kv_pc_kernel<256, true>), grid, dim3(512), smem_pc, stream, g);
-      launch_bwd_x8<4, true>(g, B, max_seqlen, stream);
+      launch_bwd_x8<true>(g, B, max_seqlen, stream);
       MI355_LAUNCH_CHECK();
       return MI355_OK;
     }
@@ -4312,42 +3679,26 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
     return MI355_OK;
   }
   if constexpr (D >= 256) {
-    constexpr int var = 1;   // (the variant bits below were sweep switches of rounds 3-4; 1 is the measured best)
-    g.bq_kv = (var & 1) ? 64 : 32;
     if (g.p_ws) {          // dK pass first (it writes P and dS), then the two one-GEMM passes
-      // 32-row steps with the next step's Q / dO rows prefetched into registers (64-row steps leave no registers for it and
-      // fetch synchronously): 0.153 -> 0.149 ms at C3, 1.33 -> 1.29 ms at L = 4096 once the elementwise phase was fixed
-      if (var & 32) { g.bq_kv = 64; launch_bwd_kv<D, 64, 2, false, true>(g, grid, stream); }
-      else {
-        g.bq_kv = 32;
-        constexpr int kvpc = 1;
-        if (kvpc) {   // the S-wave / K-wave dK pass (two waves per SIMD)
-          const size_t smem_pc = (size_t)(6 * 32 * 256 + 2 * 4 * 2 * 64 * 8) * sizeof(uint16_t);
-          static bool attr_pc = false;
-          if (!attr_pc) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_pc_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_pc);
-            attr_pc = true;
-          }
-          hipLaunchKernelGGL((hstu_bwd_kv_pc_kernel<256>), grid, dim3(512), smem_pc, stream, g);
-        } else launch_bwd_kv<D, 32, 2, true, true>(g, grid, stream);
+      // the S-wave / K-wave dK pass (two waves per SIMD) in 32-row steps.  Measured and rejected: the register-staged dK pass in
+      // 64-row steps (no registers left to prefetch the next step's Q / dO rows: 0.153 against 0.149 ms at C3, 1.33 against 1.29 ms
+      // at L = 4096), and the register-staged one-GEMM passes instead of the DMA-staged ones
+      g.bq_kv = 32;
+      const size_t smem_pc = (size_t)(6 * 32 * 256 + 2 * 4 * 2 * 64 * 8) * sizeof(uint16_t);
+      static bool attr_pc = false;
+      if (!attr_pc) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_pc_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_pc);
+        attr_pc = true;
       }
-      constexpr int x8 = 4;
-      if (x8 == 8) launch_bwd_x8<8>(g, B, max_seqlen, stream);
-      else if (x8) launch_bwd_x8<4>(g, B, max_seqlen, stream);
-      else {
-        launch_bwd_v_p<D>(g, grid, stream);
-        launch_bwd_q_ds<D>(g, grid, stream);
-      }
+      hipLaunchKernelGGL((hstu_bwd_kv_pc_kernel<256>), grid, dim3(512), smem_pc, stream, g);
+      launch_bwd_x8(g, B, max_seqlen, stream);
       MI355_LAUNCH_CHECK();
       return MI355_OK;
     }
-    if (var & 4) launch_bwd_kv<D, 64, 1, false>(g, grid, stream); else launch_bwd_kv<D, 64, 1, true>(g, grid, stream);
-    if (var & 1) launch_bwd_kv<D, 64, 2, false>(g, grid, stream);
-    else if (var & 8) launch_bwd_kv<D, 32, 2, false>(g, grid, stream);
-    else launch_bwd_kv<D, 32, 2, true>(g, grid, stream);
+    g.bq_kv = 64;
+    launch_bwd_kv<D, 64, 1, true>(g, grid, stream);
+    launch_bwd_kv<D, 64, 2, false>(g, grid, stream);
     if (g.ds_ws) launch_bwd_q_ds<D>(g, grid, stream);
-    else if (var & 2) launch_bwd_q<D, 64, false>(g, grid, stream);
-    else if (var & 16) launch_bwd_q<D, 32, false>(g, grid, stream);
     else launch_bwd_q<D, 32, true>(g, grid, stream);
   } else if constexpr (D >= 128) {
     g.bq_kv = 32;
@@ -4373,29 +3724,33 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
   return MI355_OK;
 }
 
-// the two-waves-per-SIMD forward (default at head dim 256; MI355_HSTU_PC=0 = the one-kind register-staged kernel)
+// the two-waves-per-SIMD forward (head dim 256; MI355_HSTU_FWD = 5: the one-kind register-staged kernel, see mi355_hstu_attn_fwd_kv)
 template <int D>
 static int launch_fwd_pc(const AttnArgs& a, int B, int max_seqlen, hipStream_t stream, bool dense_batch) {
   const size_t smem = (size_t)(4 * kBN * D + 2 * 4 * 4 * 64 * 8) * sizeof(uint16_t);   // K ring + V ring + P ring = 160 KB
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pc_kernel<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pc_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess) return MI355_ELAUNCH;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+      return MI355_ELAUNCH;
     attr_set = true;
   }
-  // row blocks in (heavy, light) pairs per workgroup: dense batches only (every sequence max_seqlen rows: the caller said so with
-  // mi355_hstu_attn_fwd_hint_tokens).  On a jagged batch the pairs of a long column are as heavy as before but half as many
-  // workgroups share the machine and the tail grows (C4 shape 340 -> 355 us); MI355_HSTU_PAIR = 0 never, 2 always (A/B).
   // MI355_HSTU_FWD (a TEST hook, read once): 0 / unset = the rules below; 1 = 64-row waves at every length, 2 = ... in pairs on every
   // batch, 3 = 32-row waves at every length, 4 = ... in pairs on every batch (5 = the one-kind kernel: see mi355_hstu_attn_fwd_kv)
   static const int fwd_hook = getenv("MI355_HSTU_FWD") ? atoi(getenv("MI355_HSTU_FWD")) : 0;
-  const int pair = (fwd_hook == 2 || fwd_hook == 4) ? 2 : 1;
+  // row blocks in (heavy, light) pairs per workgroup: dense batches only (every sequence max_seqlen rows: the caller said so with
+  // mi355_hstu_attn_fwd_hint_tokens).  On a jagged batch the pairs of a long column are as heavy as before but half as many
+  // workgroups share the machine and the tail grows (C4 shape 340 -> 355 us).
+  const bool paired = fwd_hook == 2 || fwd_hook == 4 || dense_batch;
   // 64 query rows per wave (two MFMAs per LDS fragment) from 1 025 rows: +4-6 % at L >= 2048, +1-4 % on jagged Zipf-to-4096 batches,
-  // level at 768-1024, -2 % at C3 and -6 % at L = 256 (fewer, larger units per short column); 2 = always, 0 = never (A/B)
-  const int q2 = (fwd_hook == 1 || fwd_hook == 2) ? 2 : ((fwd_hook == 3 || fwd_hook == 4) ? 0 : 1);
-  if (q2 == 2 || (q2 == 1 && max_seqlen > 1024) || a.func) {
+  // level at 768-1024, -2 % at C3 and -6 % at L = 256 (fewer, larger units per short column)
+  const bool q2 = fwd_hook == 1 || fwd_hook == 2 || (fwd_hook != 3 && fwd_hook != 4 && max_seqlen > 1024) || a.func;
+  const int nblk = (max_seqlen + kBM - 1) / kBM;
+  const bool win = a.wl >= 0 || a.wr >= 0;
+  const dim3 grid(a.H, B, paired ? (nblk + 1) / 2 : nblk);
+  if (q2) {
     static bool attr_q2 = false;
     if (!attr_q2) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
@@ -4405,8 +3760,6 @@ static int launch_fwd_pc(const AttnArgs& a, int B, int max_seqlen, hipStream_t s
         return MI355_ELAUNCH;
       attr_q2 = true;
     }
-    const int nblk = (max_seqlen + kBM - 1) / kBM;
-    const bool win = a.wl >= 0 || a.wr >= 0;
     if (a.func) {     // mask functions: the window-capable variants + the functions
       static bool attr_fn = false;
       if (!attr_fn) {
@@ -4415,50 +3768,29 @@ static int launch_fwd_pc(const AttnArgs& a, int B, int max_seqlen, hipStream_t s
           return MI355_ELAUNCH;
         attr_fn = true;
       }
-      if (pair == 2 || (pair == 1 && dense_batch)) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, true, true>), dim3(a.H, B, (nblk + 1) / 2), dim3(512), smem, stream, a);
-      else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, false, true>), dim3(a.H, B, nblk), dim3(512), smem, stream, a);
-      MI355_LAUNCH_CHECK();
-      return MI355_OK;
-    }
-    if (pair == 2 || (pair == 1 && dense_batch)) {
-      dim3 grid(a.H, B, (nblk + 1) / 2);
+      if (paired) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, true, true>), grid, dim3(512), smem, stream, a);
+      else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, false, true>), grid, dim3(512), smem, stream, a);
+    } else if (paired) {
       if (win) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, true>), grid, dim3(512), smem, stream, a);
       else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, false, true>), grid, dim3(512), smem, stream, a);
     } else {
-      dim3 grid(a.H, B, nblk);
       if (win) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, false>), grid, dim3(512), smem, stream, a);
       else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, false, false>), grid, dim3(512), smem, stream, a);
     }
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+  } else if (paired) {
+    if (win) hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, true, true>), grid, dim3(512), smem, stream, a);
+    else hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, false, true>), grid, dim3(512), smem, stream, a);
+  } else {
+    if (win) hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, true, false>), grid, dim3(512), smem, stream, a);
+    else hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, false, false>), grid, dim3(512), smem, stream, a);
   }
-  if (pair == 2 || (pair == 1 && dense_batch)) {
-    static bool attr_pair = false;
-    if (!attr_pair) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem) != hipSuccess) return MI355_ELAUNCH;
-      attr_pair = true;
-    }
-    const int nblk = (max_seqlen + kBM - 1) / kBM;
-    dim3 grid(a.H, B, (nblk + 1) / 2);
-    if (a.wl >= 0 || a.wr >= 0) hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, true>), grid, dim3(512), smem, stream, a);
-    else hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, false>), grid, dim3(512), smem, stream, a);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
-  }
-  dim3 grid(a.H, B, (max_seqlen + kBM - 1) / kBM);
-  if (a.wl >= 0 || a.wr >= 0) hipLaunchKernelGGL((hstu_fwd_pc_kernel<D, true>), grid, dim3(512), smem, stream, a);
-  else hipLaunchKernelGGL((hstu_fwd_pc_kernel<D, false>), grid, dim3(512), smem, stream, a);
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }
 
 template <int D>
 static int launch_fwd(const AttnArgs& a, int B, int max_seqlen, hipStream_t stream) {
-  const size_t vtile = HSTU_VTR ? (size_t)kBN * (D == 32 ? 32 : D + 32) : (size_t)D * (kBN + 8);
-  const size_t smem = (size_t)((D >= HSTU_DB_MIN ? 2 : 1) * (kBN * (D + 8) + vtile) + (D >= HSTU_QLDS_MIN ? kBM * (D + 8) : 0)) * sizeof(uint16_t);
+  const size_t smem = (size_t)(kBN * (D + 8) + D * (kBN + 8)) * sizeof(uint16_t);
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_kernel<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4494,14 +3826,6 @@ struct RabCall { const uint16_t* rab = nullptr; int64_t rb = 0, rh = 0, rr = 0; 
                  const int32_t* func = nullptr; int64_t fh = 0, fp = 0; int nf = 0; float fneg = 0.f;
                  void* kvis = nullptr; int64_t kvis_bytes = 0; };   // (backward: room for the key-block table of the func masks)
 static thread_local RabCall tl_rab;
-static int block_rotation(int heads) {   // MI355_HSTU_ROT (A/B): see seq_head_of_block; default -H = by a sequence per rank, jagged batches only
-  constexpr int v = 0x7fffffff;
-  return v == 0x7fffffff ? -heads : v;
-}
-static int column_major() {   // MI355_HSTU_CM=0: dense batches keep the rank-major grid (A/B)
-  constexpr int v = 1;
-  return v;
-}
 static int window_skip() {   // MI355_HSTU_WSKIP=0: keep the full tile loops under a window (A/B tests of the band clipping)
   static const int v = [] { const char* e = getenv("MI355_HSTU_WSKIP"); return e ? atoi(e) != 0 : 1; }();
   return v;
@@ -4509,8 +3833,7 @@ static int window_skip() {   // MI355_HSTU_WSKIP=0: keep the full tile loops und
 
 // ---- sizes of the backward's optional P / dS exchange (shared by both translation units)
 static int xch_regions(int64_t head_dim) {   // dS, and (head_dim >= 128, where dV and dK are separate passes) P behind it
-  constexpr int envp = 1;
-  return (envp && head_dim >= 128) ? 2 : 1;
+  return head_dim >= 128 ? 2 : 1;
 }
 static int64_t xch_plan_header(int64_t units) { return ((units * 8 + 255) / 256 + (units * 4 + 255) / 256 + 1) * 256; }
 static int64_t xch_unit_tiles(int64_t ng, int tri) { return tri ? ng * (ng + 1) / 2 : ng * ng; }
@@ -4574,7 +3897,7 @@ int HSTU_FN(mi355_hstu_attn_fwd_kv)(const void* q, const void* k, const void* v,
   a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = o_head_stride;
   a.cu_seqlens = cu_seqlens_q; a.num_contexts = num_contexts; a.num_targets = num_targets;
   a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
-  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = block_rotation((int)num_heads); a.colmajor = column_major(); a.max_len = (int)max_seqlen_q;
+  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = -(int)num_heads; a.colmajor = 1; a.max_len = (int)max_seqlen_q;
   a.rab = tl_rab.rab; a.rab_b = tl_rab.rb; a.rab_h = tl_rab.rh; a.rab_r = tl_rab.rr;
   a.func = tl_rab.func; a.func_h = tl_rab.fh; a.func_p = tl_rab.fp; a.n_func = tl_rab.nf; a.func_neg = tl_rab.fneg;
   a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
@@ -4725,7 +4048,7 @@ int HSTU_FN(mi355_hstu_attn_bwd)(const void* dout, const void* q, const void* k,
   a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = 0;
   a.cu_seqlens = cu_seqlens; a.num_contexts = num_contexts; a.num_targets = num_targets;
   a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
-  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = block_rotation((int)num_heads); a.colmajor = column_major(); a.max_len = (int)max_seqlen;
+  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = -(int)num_heads; a.colmajor = 1; a.max_len = (int)max_seqlen;
   a.rab = tl_rab.rab; a.rab_b = tl_rab.rb; a.rab_h = tl_rab.rh; a.rab_r = tl_rab.rr;
   a.func = tl_rab.func; a.func_h = tl_rab.fh; a.func_p = tl_rab.fp; a.n_func = tl_rab.nf; a.func_neg = tl_rab.fneg;
   a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;

@@ -1030,27 +1030,6 @@ __device__ __forceinline__ int64_t block_incl_scan_i64(int64_t v, int64_t& total
   total = tot;
   return base + incl;
 }
-__global__ void __launch_bounds__(1024) scan64_tile_sums_kernel(const int64_t* __restrict__ in, int64_t n, int64_t* __restrict__ sums) {
-  const int64_t i0 = (int64_t)blockIdx.x * kScan64Tile + threadIdx.x * 4;
-  int64_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v += i0 + k < n ? in[i0 + k] : 0;
-  int64_t tot;
-  block_incl_scan_i64(v, tot);
-  if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(1024) scan64_tiles_kernel(const int64_t* __restrict__ in, int64_t n, const int64_t* __restrict__ tile_prefix,
-                                                            int64_t* __restrict__ out) {
-  const int64_t i0 = (int64_t)blockIdx.x * kScan64Tile + threadIdx.x * 4;
-  int64_t x[4], v = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { x[k] = i0 + k < n ? in[i0 + k] : 0; v += x[k]; }
-  int64_t tot;
-  int64_t run = tile_prefix[blockIdx.x] + block_incl_scan_i64(v, tot) - v;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { if (i0 + k < n) out[i0 + k] = run; run += x[k]; }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = tile_prefix[gridDim.x];
-}
 
 // Single-pass form (round 3): ONE launch instead of three.  Every block scans its tile, publishes the tile's sum in one
 // 64-bit word (status in the top bits; the value travels IN the word, so no fence), and the first wave walks back over its
@@ -1172,20 +1151,6 @@ static int scan_i64(const int64_t* in, int64_t n, int64_t* out, hipStream_t stre
   const int64_t nt = ceil_div(n, kScan64Tile);
   int64_t* sc = scan64_scratch(nt + 2);
   if (!sc) { mi355_set_error("scan scratch allocation failed"); return MI355_ELAUNCH; }
-  constexpr int three = 0;   // (the three-launch form: kept for batches beyond the one-launch scan's capacity)
-  if (three) {
-    static thread_local int64_t* sc3 = nullptr;
-    static thread_local int64_t cap3 = 0;
-    if (2 * nt + 2 > cap3) {
-      if (sc3) (void)hipFree(sc3);
-      cap3 = 4 * nt + 8192;
-      if (hipMalloc(&sc3, cap3 * sizeof(int64_t)) != hipSuccess) { sc3 = nullptr; cap3 = 0; mi355_set_error("scan scratch allocation failed"); return MI355_ELAUNCH; }
-    }
-    hipLaunchKernelGGL(scan64_tile_sums_kernel, dim3((unsigned)nt), dim3(1024), 0, stream, in, n, sc3);
-    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, stream, sc3, nt, sc3 + nt);
-    hipLaunchKernelGGL(scan64_tiles_kernel, dim3((unsigned)nt), dim3(1024), 0, stream, in, n, sc3 + nt, out);
-    return MI355_OK;
-  }
   hipLaunchKernelGGL(scan64_chained_kernel, dim3((unsigned)nt), dim3(1024), 0, stream, in, n, out, (unsigned long long*)(sc + 2),
                      (int*)sc);
   return MI355_OK;

@@ -11,12 +11,12 @@
 // ~45 KB of LDS.  The first P blocks of the grid are partition blocks -- one per CU at P = 256, taking 4 of its 32 wave slots --, the
 // rest the gather's.  The partition work is slower than on 1 024 threads (four rounds of 256 records instead of one) and nobody
 // waits for it: it finishes under the gather.
-// MEASURED (tools/ab_probe_c.py --var MI355_PART_FUSED, profiles/r05_part_fused.txt): sequence lookups gain (8 x 16 K tokens
+// MEASURED (profiles/r05_part_fused.txt): sequence lookups gain (8 x 16 K tokens
 // 0.0761 -> 0.0679 ms: the row copy is indifferent to what shares its CU), the POOLED C2 step loses (0.1227 -> 0.1288 ms): next to
 // 24 streaming waves per CU every round trip of the partition block's chain takes 2-3x as long -- its life goes from 12 to 38 us
 // (50 for the slowest block) and the launch ends with it, 54 us against 21 + 30 apart; raising the role's wave priority changes
 // nothing, and with the gather blocks FIRST in the grid a batch whose keys all go through the eviction would deadlock on the
-// ready flags.  Hence: on by default for sequence lookups only (MI355_PART_FUSED: 0 off, 1 sequence, 2 pooled as well).
+// ready flags.  Hence: sequence lookups only.
 // A gather lane that meets an occurrence whose key went through the partition block's eviction (address word 1: bucket full) waits for
 // that partition's ready flag (LateRefs::ready); partition blocks are dispatched ahead of every gather block, so the wait cannot deadlock.
 //
@@ -43,7 +43,7 @@ __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* 
   __shared__ int b_pos[kBigMax], b_ref[kBigMax], b_cnt[kBigMax];
   const int tid = (int)threadIdx.x;
   const int64_t rec_base = (int64_t)p * CAP;
-  // a latency chain next to 24 streaming waves of the gather: its few instructions go first (MI355_PART_PRIO=0 in FusedArgs::dbg bit 2 turns it off)
+  // a latency chain next to 24 streaming waves of the gather: its few instructions go first (FusedArgs::dbg bit 2 turns it off)
   if (!(a.dbg & 4)) __builtin_amdgcn_s_setprio(3);
   QST(0);
   if (a.notice && p == 0 && tid == 0) publish_notice(a);

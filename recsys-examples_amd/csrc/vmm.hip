@@ -135,7 +135,7 @@ int mi355_vmm_destroy(void* handle) {
   if (!v->host) {
     if (v->mapped) hipMemUnmap(v->base, v->mapped);
     for (auto h : v->handles) hipMemRelease(h);
-    // The address range is NOT handed back (MI355_VMM_FREE_VA=1 does): a later reservation that lands on a freed range was seen
+    // The address range is NOT handed back: a later reservation that lands on a freed range was seen
     // to lose first-touch row stores of its first kernel -- keys found, rows zero, for a third of the rows, only when another
     // extendable buffer had been destroyed just before (round 5, tools/runs/diag_growth.py; stale translations of the old mapping
     // is the only reading that fits).  Virtual address space is not a scarce resource; the physical chunks are released above.

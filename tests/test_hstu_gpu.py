@@ -771,7 +771,7 @@ def test_rab_without_drab_and_zero_bias():
 _FWD_VARIANTS = {
     "rows64": {"MI355_HSTU_FWD": "1"},                                   # hstu_fwd_q2_kernel at every length (default: from 1 025 rows)
     "rows64_pairs": {"MI355_HSTU_FWD": "2"},                             # ... with row blocks in pairs on every batch (default: dense ones)
-    "rows32": {"MI355_HSTU_FWD": "3"},                                   # hstu_fwd_pc_kernel / hstu_fwd_pair_kernel at every length
+    "rows32": {"MI355_HSTU_FWD": "3"},                                   # hstu_fwd_pair_kernel (unpaired on jagged batches) at every length
     "rows32_pairs": {"MI355_HSTU_FWD": "4"},
     "one_stream": {"MI355_HSTU_FWD": "5"},                               # hstu_fwd_kernel, register-staged tiles
 }
@@ -779,9 +779,9 @@ _FWD_VARIANTS = {
 
 @pytest.mark.parametrize("variant", list(_FWD_VARIANTS))
 def test_forward_kernel_variants(variant):
-    """The d = 256 forward has four kernels (the one-kind LDS-DMA kernel of round 3 won on no shape and was removed in round 5).  Default since round 4: 8-wave workgroups of S waves and O waves (two waves per
+    """The d = 256 forward has three kernels (the one-kind LDS-DMA kernel of round 3 won on no shape and was removed in round 5).  Default since round 4: 8-wave workgroups of S waves and O waves (two waves per
     SIMD) -- hstu_fwd_q2_kernel (64 query rows per wave: two MFMAs per LDS fragment) from 1 025 rows per sequence,
-    hstu_fwd_pc_kernel / hstu_fwd_pair_kernel (32 rows per wave) below; row blocks in (heavy, light) pairs on dense batches.
+    hstu_fwd_pair_kernel (32 rows per wave) below; row blocks in (heavy, light) pairs on dense batches (both kernels' kPair).
     MI355_HSTU_FWD (one test hook, values 1..5) forces each of them onto every shape; 5 is the one-kind register-staged kernel.
     The library reads the hook once, so every d = 256 test of this file (goldens, random jagged batches, contexts / targets, local windows, delta-q) is
     re-run in a child process with each kernel forced onto every shape."""

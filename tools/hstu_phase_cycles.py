@@ -15,7 +15,7 @@ import mi355_native
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32); ap.add_argument("--seqlen", type=int, default=512)
 ap.add_argument("--heads", type=int, default=4); ap.add_argument("--dim", type=int, default=256)
-ap.add_argument("--pc", action="store_true", help="the two-waves-per-SIMD forward (hstu_fwd_pc_kernel: S waves / O waves; the default forward)")
+ap.add_argument("--pc", action="store_true", help="the two-waves-per-SIMD forward with 32 rows per wave (hstu_fwd_pair_kernel: S waves / O waves)")
 ap.add_argument("--q2", action="store_true", help="the 64-rows-per-wave forward (hstu_fwd_q2_kernel, the default forward since round 4)")
 ap.add_argument("--bwdpc", action="store_true", help="the S-wave / K-wave dK pass of the backward (hstu_bwd_kv_pc_kernel)")
 ap.add_argument("--bwd", action="store_true", help="the dK pass of the backward (hstu_bwd_kv_kernel, exchange mode) instead of the forward")
@@ -24,7 +24,7 @@ if a.q2:
     a.pc = True
     os.environ["MI355_HSTU_FWD"] = "1"
 elif a.pc:
-    os.environ["MI355_HSTU_FWD"] = "3"   # 32-row waves, unpaired: the stamps live in hstu_fwd_pc_kernel
+    os.environ["MI355_HSTU_FWD"] = "3"   # 32-row waves: hstu_fwd_pair_kernel (paired on this dense batch; stamps either way)
 elif not a.bwd:
     os.environ.setdefault("MI355_HSTU_FWD", "5")
 dev = torch.device("cuda")
