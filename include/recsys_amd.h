@@ -860,6 +860,27 @@ int mi355_hstu_attn_fwd_fp8(int quant_mode, const void* q, const void* k, const 
                             const int32_t* cu_seqlens_descale_vt, const int32_t* cu_seqlens_block_descale_q,
                             const int32_t* cu_seqlens_block_descale_kv, int64_t block_kv, hipStream_t stream);
 
+/* FP8 backward of self-attention: the quant_mode 0 .. 5 arms of hstu_hopper_cuda.varlen_bwd (hopper/hstu_api.cpp:809-1010;
+ * arithmetic mainloop_bwd_sm90_tma_gmma_ws.hpp:1496-2342).  dout / dout_t / q / q_t / k / k_t / v: e4m3fn bytes; dout_t,
+ * q_t, k_t are read in mode 1 only (the reference's transposed-direction quantisations, token-major here) and may be null
+ * otherwise.  dq / dk / dv: fp16 outputs.  row_strides[10] / head_strides[10] (host arrays) in the order dout, dout_t, q,
+ * q_t, k, k_t, v (bytes, multiples of 16), dq, dk, dv (elements, multiples of 4).  Masks, alpha and scaling_seqlen as
+ * mi355_hstu_attn_fwd_fp8.  Descales per mode (descale_strides[7], host, in the order q, qt, k, kt, v, do, dot):
+ * 1: descale_q / _k / _v / _do [H, >= total] (row stride), descale_qt / _kt / _dot [tiles, H, head_dim] (tile stride) with
+ * cu_seqlens_descale_qt (qt, dot) / _kt (kt); 2: [H, blocks] with cu_seqlens_block_descale_q (64-token q / dout blocks) and
+ * _kv (128-token k / v blocks); 3: [B, H]; 4: [B]; 5: [1]; mode 0 reads none.  Deterministic: no atomics, no workspace. */
+int mi355_hstu_attn_bwd_fp8(int quant_mode, const void* dout, const void* dout_t, const void* q, const void* q_t,
+                            const void* k, const void* k_t, const void* v, void* dq, void* dk, void* dv,
+                            const int64_t* row_strides, const int64_t* head_strides, const int32_t* cu_seqlens,
+                            int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                            const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                            int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen,
+                            const float* descale_q, const float* descale_qt, const float* descale_k,
+                            const float* descale_kt, const float* descale_v, const float* descale_do,
+                            const float* descale_dot, const int64_t* descale_strides,
+                            const int32_t* cu_seqlens_descale_qt, const int32_t* cu_seqlens_descale_kt,
+                            const int32_t* cu_seqlens_block_descale_q, const int32_t* cu_seqlens_block_descale_kv,
+                            hipStream_t stream);
 
 #ifdef __cplusplus
 }

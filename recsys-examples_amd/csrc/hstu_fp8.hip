@@ -1,4 +1,4 @@
-// HSTU jagged attention on FP8 (OCP e4m3fn) operands for gfx950: the quantisers and the forward.
+// HSTU jagged attention on FP8 (OCP e4m3fn) operands for gfx950: the quantisers, the forward and the backward.
 //
 // Replaces (reference): hopper/hstu_attn_interface.py:32-292 (quantize_for_two_directions, quantize_for_block_scale,
 // get_bm_and_bn_block_size_fwd, quantize_for_head_batch_tensor: Python loops over the batch) and the quant_mode >= 0 arms
@@ -514,6 +514,410 @@ static void launch_fwd(int mode, const Fp8FwdArgs& a, dim3 grid, hipStream_t st)
   }
 }
 
+
+// --------------------------------------------------------------------------------------------------------------- backward
+//
+// Two passes, both recomputing S = alpha Q K^T and dP = dO V^T on the fp8 operands (seven GEMMs instead of five, but no P /
+// dS exchange between workgroups, no atomics and no workspace):
+//  * key-major (hstu_fp8_bwd_dkdv_kernel): one workgroup = 4 waves x 32 keys = 128 keys of one (sequence, head), aligned
+//    to the sequence start so that they lie in one 128-token k / kt / v descale block; 64-query steps, aligned likewise
+//    (one 64-token q / dout block of mode 2, one 128-token qt / dout_t block of mode 1).  S and dP come out with the key in
+//    the lane and 16 queries per 32-query tile in the registers; converted, they are the B operand of
+//    dV^T += dO^T P^T and dK^T += Q^T dS^T, whose A operands are dO^T / Q^T (dout_t / qt in mode 1) transposed into LDS
+//    with the accumulator's query permutation (vt_pos), as the forward fills V^T.
+//  * query-major (hstu_fp8_bwd_dq_kernel): the forward's shape, 4 waves x 32 queries, 64-key tiles; dQ^T += K^T dS^T with
+//    K^T (kt in mode 1) transposed into LDS.
+// P and dS are divided by s = max(1e-6, max |x|) / 448 over their group before the e4m3 cast (modes 1-5; mode 0 casts
+// straight, saturating at +-448): the wave's 32 keys x 64 queries in the key-major pass, its 32 queries x 64 keys in the
+// query-major one; each tile's partial product is computed into a zeroed accumulator and added times s and the partner's
+// descale.  dS = dP SiLU'(S) alpha / N, dV = P^T dO / N; dq / dk / dv are written as fp16.
+
+struct Fp8BwdArgs {
+  const uint8_t *q, *k, *v, *dout, *qt, *kt, *dot;   // qt / kt / dot alias q / k / dout outside mode 1
+  uint16_t *dq, *dk, *dv;
+  int64_t q_rs, k_rs, v_rs, do_rs, qt_rs, kt_rs, dot_rs, dq_rs, dk_rs, dv_rs;   // token strides (bytes / fp16 elements)
+  int64_t q_hs, k_hs, v_hs, do_hs, qt_hs, kt_hs, dot_hs, dq_hs, dk_hs, dv_hs;   // head strides
+  const int32_t* cu;
+  int B, H, nqb, nkb;
+  const int32_t *nc, *nt;
+  int group, wl, wr;
+  float alpha, scaling;
+  const float *s_q, *s_qt, *s_k, *s_kt, *s_v, *s_do, *s_dot;
+  int64_t s_q_s, s_qt_s, s_k_s, s_kt_s, s_v_s, s_do_s, s_dot_s;
+  const int32_t *cu_qt, *cu_kt, *cu_bq, *cu_bkv;
+};
+
+// rows [t0, t0 + 64) of x (one head; x already offset by it) into s[64][D + 16], zero past the sequence
+template <int D>
+__device__ __forceinline__ void fill_rows(uint8_t* s, const uint8_t* x, int64_t rs, int t0, int L) {
+  for (int i = threadIdx.x; i < 64 * D / 16; i += 256) {
+    const int r = i / (D / 16), c = i % (D / 16), t = t0 + r;
+    uint4 val = make_uint4(0, 0, 0, 0);
+    if (t < L) val = *(const uint4*)(x + (int64_t)t * rs + 16 * c);
+    *(uint4*)(s + r * (D + 16) + 16 * c) = val;
+  }
+}
+// the same rows transposed into s[D][64 + 16], token t0 + k at vt_pos(k): 4 tokens x 16 columns per thread
+template <int D>
+__device__ __forceinline__ void fill_t(uint8_t* s, const uint8_t* x, int64_t rs, int t0, int L) {
+  for (int i = threadIdx.x; i < D; i += 256) {
+    const int cg = i % (D / 16), kg = i / (D / 16);
+    uint32_t rw[4][4];
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+      const int t = t0 + 4 * kg + y;
+      uint4 val = make_uint4(0, 0, 0, 0);
+      if (t < L) val = *(const uint4*)(x + (int64_t)t * rs + 16 * cg);
+      rw[y][0] = val.x; rw[y][1] = val.y; rw[y][2] = val.z; rw[y][3] = val.w;
+    }
+    const int pos = vt_pos(4 * kg);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t t = ((rw[0][u] >> (8 * e)) & 0xffu) | (((rw[1][u] >> (8 * e)) & 0xffu) << 8) |
+                           (((rw[2][u] >> (8 * e)) & 0xffu) << 16) | (((rw[3][u] >> (8 * e)) & 0xffu) << 24);
+        *(uint32_t*)(s + (16 * cg + 4 * u + e) * 80 + pos) = t;
+      }
+  }
+}
+
+__device__ __forceinline__ Mask make_mask(const Fp8BwdArgs& a, int b, int L) {
+  Mask mk;
+  mk.ctx = a.nc != nullptr;
+  mk.tgt = a.nt != nullptr;
+  mk.nc = mk.ctx ? a.nc[b] : 0;
+  mk.hist = L - (mk.tgt ? a.nt[b] : 0);
+  mk.group = a.group;
+  mk.wl = a.wl;
+  mk.wr = a.wr;
+  return mk;
+}
+// the modes-3 / 4 / 5 descale index of (sequence b, head h)
+__device__ __forceinline__ int grp_idx(int mode, int b, int h, int H) { return mode == 3 ? b * H + h : mode == 4 ? b : 0; }
+
+// x [2 tiles][16] -> e4m3 B operand; modes 1-5 divide by the group scale first (returned; 1 in mode 0)
+template <int MODE>
+__device__ __forceinline__ float to_fp8(v16f* x, float amax, v8i& f) {
+  float sc = 1.f;
+  if (MODE != 0) {
+    const float m = fmaxf(wave_max(amax), kDescaleFloor);
+    sc = m / kFp8Max;
+    const float inv = kFp8Max / m;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) x[t][r] *= inv;
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fminf(fmaxf(x[t][4 * g + e], -kFp8Max), kFp8Max);
+      f[4 * t + g] = pack4(v[0], v[1], v[2], v[3]);
+    }
+  return sc;
+}
+// acc[n] += A(n) x f, times mult (MODE 0: unscaled) or, in mode 1, times sc * col_ds[column]
+template <int D, int MODE>
+__device__ __forceinline__ void gemm_t(v16f* acc, const uint8_t* sA, v8i f, float sc, float mult, const float* col_ds,
+                                       int lr, int lh) {
+#pragma unroll
+  for (int n = 0; n < D / 32; ++n) {
+    const v8i va = lds32(sA + (32 * n + lr) * 80 + 32 * lh);
+    if (MODE == 0) {
+      acc[n] = mfma_fp8(va, f, acc[n]);
+    } else {
+      const v16f part = mfma_fp8(va, f, v16f{});
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float m = MODE == 1 ? sc * col_ds[32 * n + (r & 3) + 8 * (r >> 2) + 4 * lh] : mult;
+        acc[n][r] += part[r] * m;
+      }
+    }
+  }
+}
+// acc (lane = row, registers = columns) / div -> fp16 row of out
+template <int D>
+__device__ __forceinline__ void store_row(uint16_t* op, const v16f* acc, float div, int lh) {
+#pragma unroll
+  for (int n = 0; n < D / 32; ++n)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int col = 32 * n + 8 * g + 4 * lh;
+      const uint32_t lo = (uint32_t)f32_to_f16(acc[n][4 * g] / div) | ((uint32_t)f32_to_f16(acc[n][4 * g + 1] / div) << 16);
+      const uint32_t hi = (uint32_t)f32_to_f16(acc[n][4 * g + 2] / div) | ((uint32_t)f32_to_f16(acc[n][4 * g + 3] / div) << 16);
+      *(uint2*)(op + col) = make_uint2(lo, hi);
+    }
+}
+
+// PART: 3 computes dV and dK; at d = 256, where 2 x 128 accumulators and the S / dP tiles spill, the pass is two kernels,
+// 1 (S, dV) and 2 (S, dP, dK): eight GEMMs instead of seven.
+template <int D, int MODE, int PART>
+__global__ void __launch_bounds__(256) hstu_fp8_bwd_dkdv_kernel(Fp8BwdArgs a) {
+  constexpr int KP = D + 16, NC = D / 64, NO = D / 32;
+  constexpr bool DV = PART & 1, DK = PART & 2;
+  __shared__ __attribute__((aligned(16))) uint8_t sQ[64 * KP];
+  __shared__ __attribute__((aligned(16))) uint8_t sDo[DK ? 64 * KP : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t sQT[DK ? D * 80 : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t sDoT[DV ? D * 80 : 16];
+  __shared__ float sDq[64], sDdo[64], sDqt[MODE == 1 && DK ? D : 1], sDdot[MODE == 1 && DV ? D : 1];
+
+  const int b = blockIdx.x / a.nkb, kb = blockIdx.x % a.nkb, h = blockIdx.y;
+  const int s0 = a.cu[b], L = a.cu[b + 1] - s0;
+  const int k0 = kb * 128;
+  if (k0 >= L) return;   // uniform over the workgroup, ahead of every barrier
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int key = k0 + 32 * w + lr;
+  const bool key_ok = key < L;
+  const Mask mk = make_mask(a, b, L);
+
+  const int klast = min(k0 + 128, L) - 1;
+  int qmin = a.wr >= 0 ? max(0, k0 - a.wr) : 0;
+  const int qmax = a.wl >= 0 ? min(L, klast + a.wl + 1) : L;
+  if (mk.ctx) qmin = 0;
+  qmin &= ~63;
+
+  const uint8_t* qh = a.q + (int64_t)s0 * a.q_rs + h * a.q_hs;
+  const uint8_t* doh = a.dout + (int64_t)s0 * a.do_rs + h * a.do_hs;
+  const uint8_t* qth = a.qt + (int64_t)s0 * a.qt_rs + h * a.qt_hs;
+  const uint8_t* doth = a.dot + (int64_t)s0 * a.dot_rs + h * a.dot_hs;
+
+  // K and V: B operands, lane (key lr, half lh) holds dims 64c + 32lh .. +31
+  const uint8_t* kp = a.k + (int64_t)(s0 + key) * a.k_rs + h * a.k_hs + 32 * lh;
+  const uint8_t* vp = a.v + (int64_t)(s0 + key) * a.v_rs + h * a.v_hs + 32 * lh;
+  v8i kf[NC], vf[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    kf[c] = key_ok ? lds32(kp + 64 * c) : v8i{0, 0, 0, 0, 0, 0, 0, 0};
+    vf[c] = key_ok && DK ? lds32(vp + 64 * c) : v8i{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  float dk_key = 1.f, dv_key = 1.f, u_q = 1.f, u_do = 1.f;
+  if (MODE == 1) {
+    dk_key = key_ok ? a.s_k[h * a.s_k_s + s0 + key] : 0.f;
+    dv_key = key_ok ? a.s_v[h * a.s_v_s + s0 + key] : 0.f;
+  }
+  if (MODE == 2) {
+    dk_key = a.s_k[h * a.s_k_s + a.cu_bkv[b] + k0 / 128];
+    dv_key = a.s_v[h * a.s_v_s + a.cu_bkv[b] + k0 / 128];
+  }
+  if (MODE >= 3) {
+    const int gi = grp_idx(MODE, b, h, a.H);
+    dk_key = a.s_k[gi]; dv_key = a.s_v[gi]; u_q = a.s_q[gi]; u_do = a.s_do[gi];
+  }
+  const float dsc = a.alpha / a.scaling;
+
+  v16f dva[DV ? NO : 1], dka[DK ? NO : 1];
+#pragma unroll
+  for (int n = 0; n < NO; ++n) {
+    if (DV) dva[n] = v16f{};
+    if (DK) dka[n] = v16f{};
+  }
+
+  for (int q0 = qmin; q0 < qmax; q0 += 64) {
+    __syncthreads();
+    fill_rows<D>(sQ, qh, a.q_rs, q0, L);
+    if (DK) fill_rows<D>(sDo, doh, a.do_rs, q0, L);
+    if (DK) fill_t<D>(sQT, qth, a.qt_rs, q0, L);
+    if (DV) fill_t<D>(sDoT, doth, a.dot_rs, q0, L);
+    if (MODE == 1) {
+      if (tid < 64) {
+        const bool ok = q0 + tid < L;
+        sDq[tid] = ok ? a.s_q[h * a.s_q_s + s0 + q0 + tid] : 0.f;
+        if (DK) sDdo[tid] = ok ? a.s_do[h * a.s_do_s + s0 + q0 + tid] : 0.f;
+      }
+      const int64_t tq = (int64_t)(a.cu_qt[b] + q0 / 128);
+      for (int c = tid; c < D; c += 256) {
+        if (DK) sDqt[c] = a.s_qt[tq * a.s_qt_s + h * D + c];
+        if (DV) sDdot[c] = a.s_dot[tq * a.s_dot_s + h * D + c];
+      }
+    }
+    __syncthreads();
+
+    // S and dP, key in the lane: tile t, register r -> query q0 + 32t + (r & 3) + 8 (r >> 2) + 4 lh
+    v16f s[2] = {v16f{}, v16f{}}, dp[2] = {v16f{}, v16f{}};
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        s[t] = mfma_fp8(lds32(sQ + (32 * t + lr) * KP + 64 * c + 32 * lh), kf[c], s[t]);
+        if (DK) dp[t] = mfma_fp8(lds32(sDo + (32 * t + lr) * KP + 64 * c + 32 * lh), vf[c], dp[t]);
+      }
+    float ss = a.alpha, sd = 1.f, mq = u_q, mdo = u_do;
+    if (MODE == 2) {
+      mq = a.s_q[h * a.s_q_s + a.cu_bq[b] + q0 / 64];
+      mdo = a.s_do[h * a.s_do_s + a.cu_bq[b] + q0 / 64];
+    }
+    if (MODE >= 2) { ss *= mq * dk_key; sd = mdo * dv_key; }
+    float pmax = 0.f, dmax = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qq = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * lh, row = q0 + qq;
+        float x = s[t][r] * ss, y = dp[t][r] * sd;
+        if (MODE == 1) { x *= sDq[qq] * dk_key; if (DK) y *= sDdo[qq] * dv_key; }
+        const float sg = 1.f / (1.f + __expf(-x));
+        float p = x * sg, ds = DK ? y * sg * (1.f + x * (1.f - sg)) * dsc : 0.f;
+        if (!key_ok || row >= L || !mk(row, key)) { p = 0.f; ds = 0.f; }
+        s[t][r] = p;
+        dp[t][r] = ds;
+        pmax = fmaxf(pmax, fabsf(p));
+        dmax = fmaxf(dmax, fabsf(ds));
+      }
+    if (DV) {   // dV^T += dO^T P^T
+      v8i pf;
+      const float sp = to_fp8<MODE>(s, pmax, pf);
+      gemm_t<D, MODE>(dva, sDoT, pf, sp, sp * mdo, sDdot, lr, lh);
+    }
+    if (DK) {   // dK^T += Q^T dS^T
+      v8i df;
+      const float sds = to_fp8<MODE>(dp, dmax, df);
+      gemm_t<D, MODE>(dka, sQT, df, sds, sds * mq, sDqt, lr, lh);
+    }
+  }
+
+  if (!key_ok) return;
+  if (DV) store_row<D>(a.dv + (int64_t)(s0 + key) * a.dv_rs + h * a.dv_hs, dva, a.scaling, lh);
+  if (DK) store_row<D>(a.dk + (int64_t)(s0 + key) * a.dk_rs + h * a.dk_hs, dka, 1.f, lh);
+}
+
+template <int D, int MODE>
+__global__ void __launch_bounds__(256) hstu_fp8_bwd_dq_kernel(Fp8BwdArgs a) {
+  constexpr int KP = D + 16, NC = D / 64, NO = D / 32;
+  __shared__ __attribute__((aligned(16))) uint8_t sK[64 * KP];
+  __shared__ __attribute__((aligned(16))) uint8_t sV[64 * KP];
+  __shared__ __attribute__((aligned(16))) uint8_t sKT[D * 80];
+  __shared__ float sDk[64], sDv[64], sDkt[MODE == 1 ? D : 1];
+
+  const int b = blockIdx.x / a.nqb, qb = blockIdx.x % a.nqb, h = blockIdx.y;
+  const int s0 = a.cu[b], L = a.cu[b + 1] - s0;
+  const int r0 = qb * 128;
+  if (r0 >= L) return;   // uniform over the workgroup, ahead of every barrier
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+  const int row = r0 + 32 * w + lr;
+  const bool row_ok = row < L;
+  const Mask mk = make_mask(a, b, L);
+
+  const int rlast = min(r0 + 128, L) - 1;
+  int kmin = a.wl >= 0 ? max(0, r0 - a.wl) : 0;
+  int kmax = a.wr >= 0 ? min(L, rlast + a.wr + 1) : L;
+  if (mk.ctx && r0 < mk.nc) kmax = L;
+  kmin &= ~63;
+
+  const uint8_t* kh = a.k + (int64_t)s0 * a.k_rs + h * a.k_hs;
+  const uint8_t* vh = a.v + (int64_t)s0 * a.v_rs + h * a.v_hs;
+  const uint8_t* kth = a.kt + (int64_t)s0 * a.kt_rs + h * a.kt_hs;
+
+  // Q and dO: B operands, lane (row lr, half lh) holds dims 64c + 32lh .. +31
+  v8i qf[NC], of[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (row_ok) {
+      qf[c] = lds32(a.q + (int64_t)(s0 + row) * a.q_rs + h * a.q_hs + 64 * c + 32 * lh);
+      of[c] = lds32(a.dout + (int64_t)(s0 + row) * a.do_rs + h * a.do_hs + 64 * c + 32 * lh);
+    } else {
+      qf[c] = v8i{0, 0, 0, 0, 0, 0, 0, 0};
+      of[c] = v8i{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+  }
+  float dq_row = 1.f, ddo_row = 1.f, u_k = 1.f, u_v = 1.f;
+  if (MODE == 1) {
+    dq_row = row_ok ? a.s_q[h * a.s_q_s + s0 + row] : 0.f;
+    ddo_row = row_ok ? a.s_do[h * a.s_do_s + s0 + row] : 0.f;
+  }
+  if (MODE == 2) {   // the wave's 32 rows lie in one 64-row block
+    dq_row = a.s_q[h * a.s_q_s + a.cu_bq[b] + (r0 + 32 * w) / 64];
+    ddo_row = a.s_do[h * a.s_do_s + a.cu_bq[b] + (r0 + 32 * w) / 64];
+  }
+  if (MODE >= 3) {
+    const int gi = grp_idx(MODE, b, h, a.H);
+    dq_row = a.s_q[gi]; ddo_row = a.s_do[gi]; u_k = a.s_k[gi]; u_v = a.s_v[gi];
+  }
+  const float dsc = a.alpha / a.scaling;
+
+  v16f dqa[NO];
+#pragma unroll
+  for (int n = 0; n < NO; ++n) dqa[n] = v16f{};
+
+  for (int kt = kmin; kt < kmax; kt += 64) {
+    __syncthreads();
+    fill_rows<D>(sK, kh, a.k_rs, kt, L);
+    fill_rows<D>(sV, vh, a.v_rs, kt, L);
+    fill_t<D>(sKT, kth, a.kt_rs, kt, L);
+    if (MODE == 1) {
+      if (tid < 64) {
+        const bool ok = kt + tid < L;
+        sDk[tid] = ok ? a.s_k[h * a.s_k_s + s0 + kt + tid] : 0.f;
+        sDv[tid] = ok ? a.s_v[h * a.s_v_s + s0 + kt + tid] : 0.f;
+      }
+      const int64_t tk = (int64_t)(a.cu_kt[b] + kt / 128);
+      for (int c = tid; c < D; c += 256) sDkt[c] = a.s_kt[tk * a.s_kt_s + h * D + c];
+    }
+    __syncthreads();
+
+    // S^T and dP^T, query in the lane: tile t, register r -> key kt + 32t + (r & 3) + 8 (r >> 2) + 4 lh
+    v16f s[2] = {v16f{}, v16f{}}, dp[2] = {v16f{}, v16f{}};
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        s[t] = mfma_fp8(lds32(sK + (32 * t + lr) * KP + 64 * c + 32 * lh), qf[c], s[t]);
+        dp[t] = mfma_fp8(lds32(sV + (32 * t + lr) * KP + 64 * c + 32 * lh), of[c], dp[t]);
+      }
+    float ss = a.alpha, sd = 1.f, mk_ = u_k;
+    if (MODE == 2) {
+      mk_ = a.s_k[h * a.s_k_s + a.cu_bkv[b] + kt / 128];
+      u_v = a.s_v[h * a.s_v_s + a.cu_bkv[b] + kt / 128];
+    }
+    if (MODE >= 2) { ss *= dq_row * mk_; sd = ddo_row * u_v; }
+    float dmax = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kk = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * lh, key = kt + kk;
+        float x = s[t][r] * ss, y = dp[t][r] * sd;
+        if (MODE == 1) { x *= dq_row * sDk[kk]; y *= ddo_row * sDv[kk]; }
+        const float sg = 1.f / (1.f + __expf(-x));
+        float ds = y * sg * (1.f + x * (1.f - sg)) * dsc;
+        if (!row_ok || key >= L || !mk(row, key)) ds = 0.f;
+        dp[t][r] = ds;
+        dmax = fmaxf(dmax, fabsf(ds));
+      }
+    v8i df;
+    const float sds = to_fp8<MODE>(dp, dmax, df);
+    gemm_t<D, MODE>(dqa, sKT, df, sds, sds * mk_, sDkt, lr, lh);   // dQ^T += K^T dS^T
+  }
+
+  if (!row_ok) return;
+  store_row<D>(a.dq + (int64_t)(s0 + row) * a.dq_rs + h * a.dq_hs, dqa, 1.f, lh);
+}
+
+template <int D, int MODE>
+static void launch_bwd_mode(const Fp8BwdArgs& a, dim3 gk, dim3 gq, hipStream_t st) {
+  if constexpr (D == 256) {
+    hstu_fp8_bwd_dkdv_kernel<D, MODE, 1><<<gk, 256, 0, st>>>(a);
+    hstu_fp8_bwd_dkdv_kernel<D, MODE, 2><<<gk, 256, 0, st>>>(a);
+  } else {
+    hstu_fp8_bwd_dkdv_kernel<D, MODE, 3><<<gk, 256, 0, st>>>(a);
+  }
+  hstu_fp8_bwd_dq_kernel<D, MODE><<<gq, 256, 0, st>>>(a);
+}
+template <int D>
+static void launch_bwd(int mode, const Fp8BwdArgs& a, dim3 gk, dim3 gq, hipStream_t st) {
+  switch (mode) {
+    case 0: launch_bwd_mode<D, 0>(a, gk, gq, st); break;
+    case 1: launch_bwd_mode<D, 1>(a, gk, gq, st); break;
+    case 2: launch_bwd_mode<D, 2>(a, gk, gq, st); break;
+    case 3: launch_bwd_mode<D, 3>(a, gk, gq, st); break;
+    case 4: launch_bwd_mode<D, 4>(a, gk, gq, st); break;
+    default: launch_bwd_mode<D, 5>(a, gk, gq, st); break;
+  }
+}
+
 }  // namespace hstu_fp8
 }  // namespace mi355
 
@@ -597,6 +1001,78 @@ extern "C" int mi355_hstu_attn_fwd_fp8(int quant_mode, const void* q, const void
   if (head_dim == 64) launch_fwd<64>(quant_mode, a, grid, stream);
   else if (head_dim == 128) launch_fwd<128>(quant_mode, a, grid, stream);
   else launch_fwd<256>(quant_mode, a, grid, stream);
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
+}
+
+extern "C" int mi355_hstu_attn_bwd_fp8(int quant_mode, const void* dout, const void* dout_t, const void* q, const void* q_t,
+                                       const void* k, const void* k_t, const void* v, void* dq, void* dk, void* dv,
+                                       const int64_t* row_strides, const int64_t* head_strides, const int32_t* cu_seqlens,
+                                       int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                                       const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                                       int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen,
+                                       const float* descale_q, const float* descale_qt, const float* descale_k,
+                                       const float* descale_kt, const float* descale_v, const float* descale_do,
+                                       const float* descale_dot, const int64_t* descale_strides,
+                                       const int32_t* cu_seqlens_descale_qt, const int32_t* cu_seqlens_descale_kt,
+                                       const int32_t* cu_seqlens_block_descale_q, const int32_t* cu_seqlens_block_descale_kv,
+                                       hipStream_t stream) {
+  MI355_CHECK_ARG(quant_mode >= 0 && quant_mode <= 5, "hstu_attn_bwd_fp8: quant_mode must be 0 .. 5");
+  MI355_CHECK_ARG(dout && q && k && v && dq && dk && dv && cu_seqlens && row_strides && head_strides,
+                  "hstu_attn_bwd_fp8: null tensor or stride array");
+  MI355_CHECK_ARG(quant_mode != 1 || (dout_t && q_t && k_t), "hstu_attn_bwd_fp8: mode 1 needs dout_t, q_t and k_t");
+  MI355_CHECK_ARG(head_dim == 64 || head_dim == 128 || head_dim == 256, "hstu_attn_bwd_fp8: head_dim must be 64, 128 or 256");
+  MI355_CHECK_ARG(batch > 0 && num_heads > 0 && num_heads < 65536 && max_seqlen >= 0,
+                  "hstu_attn_bwd_fp8: bad batch / heads / max_seqlen");
+  if (quant_mode != 1) { dout_t = dout; q_t = q; k_t = k; }
+  const void* in[7] = {dout, dout_t, q, q_t, k, k_t, v};
+  int64_t acc = 0;
+  uintptr_t pacc = 0;
+  for (int i = 0; i < 7; ++i) { acc |= row_strides[i] | head_strides[i]; pacc |= (uintptr_t)in[i]; }
+  MI355_CHECK_ARG((acc & 15) == 0 && (pacc & 15) == 0,
+                  "hstu_attn_bwd_fp8: fp8 operand strides and pointers must be 16-byte aligned");
+  MI355_CHECK_ARG(((row_strides[7] | row_strides[8] | row_strides[9] | head_strides[7] | head_strides[8] | head_strides[9]) &
+                   3) == 0 && (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7) == 0,
+                  "hstu_attn_bwd_fp8: dq / dk / dv strides must be multiples of 4 elements");
+  MI355_CHECK_ARG(quant_mode == 0 || (descale_q && descale_k && descale_v && descale_do && descale_strides),
+                  "hstu_attn_bwd_fp8: descale tensors missing");
+  MI355_CHECK_ARG(quant_mode != 1 || (descale_qt && descale_kt && descale_dot && cu_seqlens_descale_qt && cu_seqlens_descale_kt),
+                  "hstu_attn_bwd_fp8: mode 1 needs descale_qt / descale_kt / descale_dot and their cu_seqlens");
+  MI355_CHECK_ARG(quant_mode != 2 || (cu_seqlens_block_descale_q && cu_seqlens_block_descale_kv),
+                  "hstu_attn_bwd_fp8: mode 2 needs the block cu_seqlens");
+  MI355_CHECK_ARG(num_targets == nullptr || target_group_size >= 1, "hstu_attn_bwd_fp8: target_group_size must be >= 1");
+  MI355_CHECK_ARG(scaling_seqlen != 0.f, "hstu_attn_bwd_fp8: scaling_seqlen is 0");
+  if (max_seqlen == 0) return MI355_OK;
+  Fp8BwdArgs a;
+  a.dout = (const uint8_t*)dout; a.dot = (const uint8_t*)dout_t; a.q = (const uint8_t*)q; a.qt = (const uint8_t*)q_t;
+  a.k = (const uint8_t*)k; a.kt = (const uint8_t*)k_t; a.v = (const uint8_t*)v;
+  a.dq = (uint16_t*)dq; a.dk = (uint16_t*)dk; a.dv = (uint16_t*)dv;
+  a.do_rs = row_strides[0]; a.dot_rs = row_strides[1]; a.q_rs = row_strides[2]; a.qt_rs = row_strides[3];
+  a.k_rs = row_strides[4]; a.kt_rs = row_strides[5]; a.v_rs = row_strides[6];
+  a.dq_rs = row_strides[7]; a.dk_rs = row_strides[8]; a.dv_rs = row_strides[9];
+  a.do_hs = head_strides[0]; a.dot_hs = head_strides[1]; a.q_hs = head_strides[2]; a.qt_hs = head_strides[3];
+  a.k_hs = head_strides[4]; a.kt_hs = head_strides[5]; a.v_hs = head_strides[6];
+  a.dq_hs = head_strides[7]; a.dk_hs = head_strides[8]; a.dv_hs = head_strides[9];
+  if (quant_mode != 1) {   // (the aliases' strides are the originals')
+    a.dot_rs = a.do_rs; a.qt_rs = a.q_rs; a.kt_rs = a.k_rs; a.dot_hs = a.do_hs; a.qt_hs = a.q_hs; a.kt_hs = a.k_hs;
+  }
+  a.cu = cu_seqlens; a.B = (int)batch; a.H = (int)num_heads;
+  a.nqb = a.nkb = (int)ceil_div(max_seqlen, 128);
+  a.nc = num_contexts; a.nt = num_targets; a.group = (int)target_group_size;
+  a.wl = window_left < 0 ? -1 : (int)window_left; a.wr = window_right < 0 ? -1 : (int)window_right;
+  a.alpha = alpha; a.scaling = scaling_seqlen;
+  a.s_q = descale_q; a.s_qt = descale_qt; a.s_k = descale_k; a.s_kt = descale_kt; a.s_v = descale_v; a.s_do = descale_do;
+  a.s_dot = descale_dot;
+  const int64_t zero[7] = {0, 0, 0, 0, 0, 0, 0};
+  const int64_t* ds = descale_strides ? descale_strides : zero;
+  a.s_q_s = ds[0]; a.s_qt_s = ds[1]; a.s_k_s = ds[2]; a.s_kt_s = ds[3]; a.s_v_s = ds[4]; a.s_do_s = ds[5]; a.s_dot_s = ds[6];
+  a.cu_qt = cu_seqlens_descale_qt; a.cu_kt = cu_seqlens_descale_kt;
+  a.cu_bq = cu_seqlens_block_descale_q; a.cu_bkv = cu_seqlens_block_descale_kv;
+  MI355_CHECK_ARG(batch * a.nqb < (1ll << 31), "hstu_attn_bwd_fp8: grid too large");
+  const dim3 grid((unsigned)(batch * a.nqb), (unsigned)num_heads);
+  if (head_dim == 64) launch_bwd<64>(quant_mode, a, grid, grid, stream);
+  else if (head_dim == 128) launch_bwd<128>(quant_mode, a, grid, grid, stream);
+  else launch_bwd<256>(quant_mode, a, grid, grid, stream);
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }

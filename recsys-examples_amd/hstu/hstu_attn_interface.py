@@ -474,16 +474,19 @@ class HstuAttnRabFunc(torch.autograd.Function):
 def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k,
                           scaling_seqlen, num_contexts, num_targets, target_group_size=1, window_size=(-1, -1), alpha=1.0,
                           rab=None, has_drab=False, kv_cache=None, page_offsets=None, page_ids=None, last_page_lens=None,
-                          func=None, quant_mode=-1):
+                          func=None, quant_mode=-1, *, fp8_backward=False):
     """out (total_q, nheads, head_dim) = HSTU attention over the jagged batch described by cu_seqlens.
 
     quant_mode 0 .. 5: q / k / v are quantised to float8_e4m3fn as the reference's modes do and the attention runs on the fp8
-    operands (hstu_fp8.py); the output is fp16.  Its backward is the bf16 / fp16 backward at the unquantised inputs with dout
-    cast to their dtype (straight-through: no FP8 backward kernels).  -1 (the default) and None: no quantisation."""
+    operands (hstu_fp8.py); the output is fp16.  Its backward is by default the bf16 / fp16 backward at the unquantised inputs
+    with dout cast to their dtype (straight-through); fp8_backward=True runs the reference's FP8 backward instead (q / k / v /
+    dout quantised in the same mode, hstu_fp8.varlen_bwd).  -1 (the default) and None: no quantisation."""
     if quant_mode is None:
         quant_mode = -1
     if isinstance(quant_mode, bool) or not isinstance(quant_mode, int) or not -1 <= quant_mode <= 5:
         raise ValueError(f"quant_mode must be -1 (none) or 0 .. 5, got {quant_mode!r}")
+    if fp8_backward and quant_mode < 0:
+        raise ValueError("fp8_backward=True needs quant_mode 0 .. 5 (there is no FP8 backward without FP8 quantisation)")
     causal = _check_inputs(q, k, v, cu_seqlens_q, cu_seqlens_k, num_contexts, num_targets, window_size, rab, kv_cache,
                            seqused_q, seqused_k)
     if max_seqlen_q > max_seqlen_k:
@@ -510,7 +513,7 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
         if q.shape[-1] == 32:
             raise NotImplementedError("head dimension 32 is not supported with quant_mode >= 0 (FP8: 64, 128, 256)")
         return HstuAttnFp8Func.apply(q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
-                                     int(target_group_size), wl, wr, float(alpha), quant_mode)
+                                     int(target_group_size), wl, wr, float(alpha), quant_mode, bool(fp8_backward))
     if func is not None and rab is None:
         # arbitrary mask functions, read inside the kernels (round 5; MI355_HSTU_FUNC_DENSE=1 keeps the dense-bias statement below,
         # the two agree bit for bit): they narrow whatever other mask applies, as in the reference (hstu_fwd.h:519-556) -- except

@@ -176,6 +176,9 @@ _SIGS = {
     "mi355_hstu_attn_fwd_fp8": [c_int, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64,
                                 c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p, c_i64, c_i64,
                                 c_i64, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_attn_bwd_fp8": [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64,
+                                c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                c_p, c_p, c_p, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
