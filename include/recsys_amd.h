@@ -447,6 +447,17 @@ int mi355_side_join(int token, hipStream_t stream);
  * 64 K .. 1 M keys and at least 8 buckets per partition take the partitioned index stage: (tile, key) records grouped by
  * slot range, one block per range merges them in LDS -- no global atomic per key, no per-slot scratch. */
 int mi355_demb_forward_fused_partitions(int64_t n, int64_t num_tables, int64_t num_buckets);
+
+/* Per-key frequency weights (the reference's per_sample_weights / frequency_counters: counts, not pooling weights).  Binds
+ * `weights` (int64 [num_keys], device) to the NEXT index stage the calling thread issues -- mi355_demb_forward,
+ * mi355_demb_forward_fused(_rerun), mi355_demb_plan_forward / _stage / _rerun --, which consumes the binding; a plan call that
+ * returns MI355_ENOSPC (nothing launched) keeps it.  A counting score policy (Accumulate; LRU_LFU's frequency word), the insert of
+ * an unseen key and the admission counter then add the SUM of a key's weights where they add its occurrence count otherwise.
+ * Outputs, gradients, the other score policies and eval forwards do not see them.  Negative weights are the caller's error.
+ * workspace: mi355_demb_weights_workspace_bytes(num_keys, num_tables) bytes of device scratch, untouched until the bound call's
+ * kernels have run. */
+int64_t mi355_demb_weights_workspace_bytes(int64_t num_keys, int64_t num_tables);
+int mi355_demb_bind_weights(const int64_t* weights, int64_t num_keys, void* workspace, int64_t workspace_bytes);
 /* Round 3: a pooled training forward of the partitioned stage (path (c), MI355_FUSED_PART=2) returns *join_token == -2.  Its
  * partition kernel wrote the backward's CSR itself (no scatter kernel); the per-occurrence outputs nothing on the training path reads --
  * reverse_indices (the `inverse` of segmented_unique_cuda, src/unique_op.cu:484-714) and csr_rank -- are produced by this call

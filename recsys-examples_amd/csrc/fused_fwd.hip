@@ -135,15 +135,21 @@ struct FusedArgs {
   int tl;                         // probe_c_kernel (round 5): keys of a tile, a run-time value (<= the kernel's capacity, multiple of 64)
   int cap;                        // records per partition of `rec` (kPartCap)
   int32_t* part_ready;            // [P] (round 5, the partition blocks riding in the gather's launch): 1 once partition p's deferred keys
-                                  // have their slots in the records (zeroed by the probe kernel; nullable)
+                                  // have their slots in the records (zeroed by the probe kernel; nullable)  // per-key frequency weights (the weighted instantiations, kW): a counting score policy and the deferred inserts add the SUM of a
+  // key's weights where they add its occurrence count otherwise (the reference's per_sample_weights / frequency_counters)
+  const int64_t* wts;             // [n] weight of every occurrence (nullptr: unweighted)
+  int64_t* rec_w;                 // [P * kPartCap] weight sum of every record (path (c); the record itself carries the occurrences)
+  int64_t* d_w;                   // [n] weight sum of every deferred key (path (b))
 };
 
 __device__ __forceinline__ void store_digest(uint8_t* p, uint8_t d) {
   __hip_atomic_store(p, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// score of a key that is already stored (score.cuh:72-96); `cnt` = occurrences of the key in the caller's tile
-__device__ __forceinline__ void score_found(const FusedArgs& a, uint64_t* sc, int cnt) {
+// score of a key that is already stored (score.cuh:72-96); `cnt` = occurrences of the key in the caller's tile (int), or the sum
+// of their weights (int64_t, the weighted instantiations)
+template <typename CntT>
+__device__ __forceinline__ void score_found(const FusedArgs& a, uint64_t* sc, CntT cnt) {
   const uint64_t v = a.use_count ? (uint64_t)cnt : a.score_value;
   switch (a.find_policy) {
     // Assign / timer scores are idempotent and nobody reads a score before the next kernel: plain (write-back cached)
@@ -157,7 +163,8 @@ __device__ __forceinline__ void score_found(const FusedArgs& a, uint64_t* sc, in
   }
 }
 // score of a key placed in a fresh (or evicted and cleared) slot: Accumulate acts as Assign (key_value_table.py:881-925)
-__device__ __forceinline__ void score_new(const FusedArgs& a, uint64_t* sc, int cnt) {
+template <typename CntT>
+__device__ __forceinline__ void score_new(const FusedArgs& a, uint64_t* sc, CntT cnt) {
   const uint64_t v = a.use_count ? (uint64_t)cnt : a.score_value;
   switch (a.insert_policy) {
     case kConst: ast64(sc, 0); break;
@@ -170,8 +177,8 @@ __device__ __forceinline__ void score_new(const FusedArgs& a, uint64_t* sc, int 
 // One lane probes one key (types.cuh:308-396 order: 16-aligned start, wrap around; inside a 16-slot vector first the
 // slots whose digest matches, then the first Empty one).  kInsert: an absent key takes the first Empty slot.
 // Returns the slot, -1 (absent, lookup only) or -2 (no Empty slot in the bucket / gave up on a stuck lock).
-template <bool kInsert>
-__device__ __forceinline__ int thread_probe(const FusedArgs& a, int64_t b, uint64_t key, int64_t hash, int cnt, bool& inserted) {
+template <bool kInsert, typename CntT = int>
+__device__ __forceinline__ int thread_probe(const FusedArgs& a, int64_t b, uint64_t key, int64_t hash, CntT cnt, bool& inserted) {
   const Table& t = a.t;
   const int C = (int)t.C;
   const uint32_t d = digest_of(hash);
@@ -261,7 +268,10 @@ __device__ __forceinline__ void wave_init_row(const FusedArgs& a, void* rp, uint
 // kMT (round 4, with kPart + kBags): table-aligned partitions of a multi-table batch (FusedArgs::mt).
 // kSeq (round 4, with kBags): sequence lookups -- the "bag" of occurrence j is j itself (the backward's CSR lists gradient rows),
 // so the bag search and the running maximum over the bag marks fall away.
-template <int TILE, int THREADS, bool kTrain, bool kPart = false, bool kFast = false, bool kBags = false, bool kMT = false, bool kSeq = false>
+// kW: per-key frequency weights (FusedArgs::wts): an int64 weight sum per dedup entry (s_w) is what a counting score policy adds and
+// what a deferred key / a record carries for its insert (d_w / rec_w); s_cnt stays the occurrence count.
+template <int TILE, int THREADS, bool kTrain, bool kPart = false, bool kFast = false, bool kBags = false, bool kMT = false, bool kSeq = false,
+          bool kW = false>
 __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
   constexpr bool kOne = kPart && !kMT;             // the one-table forms of the partitioned paths keep the table's scalars in registers
   __shared__ int s_pt[kMT ? kFusedMaxT : 1];       // kMT: partitions of every table
@@ -282,6 +292,7 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
   __shared__ uint64_t s_key[TILE];
   __shared__ int s_tab[LDS];        // dedup: tile position of the key's representative; after the probe: its global slot
   __shared__ int s_cnt[LDS];        // dedup: occurrences inside the tile; after the probe: rank base of the tile
+  __shared__ int64_t s_w[kW ? LDS : 1];   // (kW) dedup: weight sum of the key's occurrences inside the tile
   __shared__ uint16_t s_t[TILE];    // table of every key (bit 15: representative whose row is new)
   __shared__ int s_gs[TILE];        // global slot of new rows (by representative position)
   __shared__ int64_t s_seg[kFusedMaxT + 1];
@@ -296,10 +307,12 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
   // per-table metadata next (one hop, or none for a single table), and the first digest vector of EVERY key is fetched
   // before the LDS dedup -- speculative for the duplicates, but the dedup then runs in the shadow of that load.
   uint64_t kreg[PER];
+  int64_t wreg[kW ? PER : 1];
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const int64_t i = tile0 + q * THREADS + threadIdx.x;
     kreg[q] = a.keys[i < a.n ? i : a.n - 1];
+    if constexpr (kW) wreg[q] = a.wts[i < a.n ? i : a.n - 1];
   }
   // kPart (one table): the table's scalars come straight from memory with uniform loads issued here and used two phases later --
   // staged through LDS by threads 0 / 1 they were a global round trip in front of the FIRST barrier of every block
@@ -359,7 +372,7 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
       }
     }
   }
-  for (int s = threadIdx.x; s < LDS; s += THREADS) { s_tab[s] = -1; s_cnt[s] = 0; }
+  for (int s = threadIdx.x; s < LDS; s += THREADS) { s_tab[s] = -1; s_cnt[s] = 0; if constexpr (kW) s_w[s] = 0; }
   if (threadIdx.x < HALVES) s_nrep[threadIdx.x] = 0;
   if constexpr (kPart) for (int p = threadIdx.x; p < a.P; p += THREADS) s_hist[p] = 0;
   __syncthreads();
@@ -466,6 +479,7 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
       }
       hh[q] = h;
       rk[q] = atomicAdd(&s_cnt[h], 1);
+      if constexpr (kW) atomicAdd((unsigned long long*)&s_w[h], (unsigned long long)wreg[q]);
     }
   }
   PST(4);
@@ -574,6 +588,10 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
     const uint64_t key = kreg[q];
     const int t = s_t[li];
     const int cnt = s_cnt[hh[q]];
+    // what a counting score policy adds: the occurrences, or (kW) the sum of their weights
+    using IncT = typename std::conditional<kW, int64_t, int>::type;
+    IncT inc;
+    if constexpr (kW) inc = s_w[hh[q]]; else inc = cnt;
     if constexpr (kPart) cnt_tile[q] = cnt;
     int gslot = (int)a.S, base = 0;     // default: no slot
     bool defer = false;
@@ -585,11 +603,11 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
       int slot;
       if (a.dbg & 2) slot = (int)((uint64_t)hq[q] & (uint64_t)(a.t.C - 1));
       else if (cand[q] >= 0 && kc[q] == key) slot = cand[q];
-      else slot = thread_probe<kTrain>(a, b, key, hq[q], cnt, inserted);
+      else slot = thread_probe<kTrain>(a, b, key, hq[q], inc, inserted);
       if (slot >= 0) {
         gslot = (int)(b * a.t.C + slot);
         if (inserted) { s_t[li] = (uint16_t)(t | 0x8000); s_gs[li] = gslot; }
-        else if (!idem) score_found(a, a.t.scores(b) + (int64_t)slot * a.t.ns, cnt);
+        else if (!idem) score_found(a, a.t.scores(b) + (int64_t)slot * a.t.ns, inc);
         else found_sc = a.t.scores(b) + (int64_t)slot * a.t.ns;
       } else if (slot == -2) {
         defer = true;
@@ -607,6 +625,7 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
       if (defer) {
         const int e = atomicAdd(&a.hdr[0], 1);
         a.d_key[e] = key; a.d_tid[e] = t; a.d_cnt[e] = cnt;
+        if constexpr (kW) a.d_w[e] = inc;
         gslot = -(e + 2);
       } else {
         base = (a.dbg & 1) ? 0 : atomicAdd(&a.occ[2 * (int64_t)gslot], cnt);
@@ -643,6 +662,7 @@ __global__ void __launch_bounds__(THREADS) fused_probe_kernel(FusedArgs a) {
                                   (uint32_t)s_cnt[hh[q]], (uint32_t)cnt_tile[q]);
         } else
         a.rec[ref] = make_uint4((uint32_t)kreg[q], (uint32_t)(kreg[q] >> 32), (uint32_t)s_cnt[hh[q]], (uint32_t)cnt_tile[q]);
+        if constexpr (kW) a.rec_w[ref] = s_w[hh[q]];
       } else {
         a.hdr[a.ovf_word] = a.ovf_val;     // a partition received more records than it can hold: the step is flagged (see the module)
       }
@@ -752,6 +772,7 @@ __device__ __forceinline__ void grid_sync_reset(int* hdr) {
   for (int g = 0; g < ngroups; ++g) hdr[8 + g] = 0;
 }
 
+template <bool kW = false>   // kW: the deferred keys' weight sums (FusedArgs::d_w) score their inserts
 __device__ __forceinline__ void evict_phase(const FusedArgs& a, int nd, int nblk) {
   const int g = lane_id() & (G - 1);
   const int gpb = blockDim.x / G;
@@ -762,6 +783,10 @@ __device__ __forceinline__ void evict_phase(const FusedArgs& a, int nd, int nblk
     const uint64_t key = act ? a.d_key[e] : kEmptyKey;
     const int tid = act ? a.d_tid[e] : 0;
     const int cnt = act ? a.d_cnt[e] : 0;
+    // what a counting score policy adds: the occurrences, or (kW) their weight sum
+    using IncT = typename std::conditional<kW, int64_t, int>::type;
+    IncT inc;
+    if constexpr (kW) inc = act ? a.d_w[e] : 0; else inc = cnt;
     Located L = locate(key, tid, a.tbo, a.t.C);
     int gslot = (int)a.S;
     bool done = !(act && L.ok);
@@ -779,13 +804,13 @@ __device__ __forceinline__ void evict_phase(const FusedArgs& a, int nd, int nblk
           bool fresh_row = false;
           if (found_slot >= 0) {             // another deferred entry of the same key got here first
             slot = found_slot;
-            if (g == 0) score_found(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, cnt);
+            if (g == 0) score_found(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, inc);
           } else if (empty_slot >= 0) {      // a slot was freed meanwhile
             slot = empty_slot;
             fresh_row = true;
             if (g == 0) {
               store_digest(a.t.dig(L.bucket) + slot, digest_of(L.hash));
-              score_new(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, cnt);
+              score_new(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, inc);
               atomicAdd(&a.bucket_sizes[L.bucket], 1);
             }
           } else {
@@ -816,7 +841,7 @@ __device__ __forceinline__ void evict_phase(const FusedArgs& a, int nd, int nblk
                 ast64(ks + slot, kLockedKey);
                 store_digest(a.t.dig(L.bucket) + slot, digest_of(L.hash));
                 for (int64_t w = 0; w < a.t.ns; ++w) ast64((uint64_t*)sc + (int64_t)slot * a.t.ns + w, 0);
-                score_new(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, cnt);
+                score_new(a, a.t.scores(L.bucket) + (int64_t)slot * a.t.ns, inc);
                 if (bkey == kReclaimKey) atomicAdd(&a.bucket_sizes[L.bucket], 1);
               }
             }
@@ -983,7 +1008,7 @@ __device__ __forceinline__ int lookback_prefix(unsigned long long* tstat, int t,
   return (int)lookback_prefix64(tstat, t, (unsigned long long)(unsigned)my_sum);
 }
 
-template <bool kSelf>
+template <bool kSelf, bool kW = false>   // kW: weighted deferred keys (evict_phase)
 __global__ void __launch_bounds__(kScanThreads)
 fused_mid_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, HotList hot, bool build_hot, int resident) {
   __shared__ int s_ex[kScanTile + 1];       // exclusive representative count in front of every item of the tile
@@ -1022,7 +1047,7 @@ fused_mid_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, HotList hot, boo
     if ((int64_t)nd > a.n) nd = (int)a.n;
     const int R = (int)gridDim.x < resident ? (int)gridDim.x : resident;
     if ((int)blockIdx.x < R) {
-      evict_phase(a, nd, R);
+      evict_phase<kW>(a, nd, R);
       grid_sync(a.hdr, 1, R);
       patch_phase(a, R);
       grid_sync(a.hdr, 2, R);
@@ -1268,7 +1293,7 @@ __device__ __forceinline__ void lookback_sum2_1024(const unsigned long long* ta,
 #else
 #define P3_EVICT_ATTR __forceinline__
 #endif
-template <int HASH, typename DRec, int THREADS = kP3Threads>
+template <int HASH, typename DRec, int THREADS = kP3Threads, bool kW = false>
 __device__ P3_EVICT_ATTR void part_evict(FusedArgs& a, int nd, int64_t rec_base, const DRec* d_rec, int* d_ent, int* d_base, int* s_lock,
                                            unsigned* s_late, int* h_slot, int* h_cnt, int tbl, int64_t tp0, int64_t rowb, int64_t s0,
                                            const uint64_t* d_key = nullptr, const int2* d_zw = nullptr, unsigned* s_fresh = nullptr) {
@@ -1298,6 +1323,10 @@ __device__ P3_EVICT_ATTR void part_evict(FusedArgs& a, int nd, int64_t rec_base,
           key = a.keys[kp];
           cnt = (int)rd.w; zc = (int)rd.z;
         }
+        // what a counting score policy adds: the record's occurrences, or (kW) their weight sum
+        using IncT = typename std::conditional<kW, int64_t, int>::type;
+        IncT inc;
+        if constexpr (kW) inc = act ? a.rec_w[r] : 0; else inc = cnt;
         const int64_t bucket = act ? -(int64_t)zc - 2 : 0;
         const int64_t hash = (int64_t)(fmix64(key) & 0x7FFFFFFFFFFFFFFFull);
         bool done = !act;
@@ -1320,13 +1349,13 @@ __device__ P3_EVICT_ATTR void part_evict(FusedArgs& a, int nd, int64_t rec_base,
               bool fresh_row = false;
               if (found_slot >= 0) {             // another record of the same key got here first
                 slot = found_slot;
-                if (g == 0) score_found(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, cnt);
+                if (g == 0) score_found(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, inc);
               } else if (empty_slot >= 0) {      // a slot was freed meanwhile
                 slot = empty_slot;
                 fresh_row = true;
                 if (g == 0) {
                   store_digest(a.t.dig(bucket) + slot, digest_of(hash));
-                  score_new(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, cnt);
+                  score_new(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, inc);
                   atomicAdd(&a.bucket_sizes[bucket], 1);
                 }
               } else {
@@ -1378,7 +1407,7 @@ __device__ P3_EVICT_ATTR void part_evict(FusedArgs& a, int nd, int64_t rec_base,
                     ast64(ks + slot, kLockedKey);
                     store_digest(a.t.dig(bucket) + slot, digest_of(hash));
                     for (int64_t w = 0; w < a.t.ns; ++w) ast64((uint64_t*)sc + (int64_t)slot * a.t.ns + w, 0);
-                    score_new(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, cnt);
+                    score_new(a, a.t.scores(bucket) + (int64_t)slot * a.t.ns, inc);
                     if (bkey == kReclaimKey) atomicAdd(&a.bucket_sizes[bucket], 1);
                   }
                 }
@@ -1469,7 +1498,7 @@ __device__ __forceinline__ void publish_notice(const FusedArgs& a) {
   __hip_atomic_store(a.notice, (unsigned long long)(unsigned)a.ovf_val | (f << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int CAP>
+template <int CAP, bool kW = false>   // kW: the records' weight sums (FusedArgs::rec_w) score the deferred inserts
 __global__ void __launch_bounds__(kP3Threads)
 fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restrict__ csr_src, HotList hot) {
   constexpr int kPartCap = CAP, kSubCap = CAP / kPartSub, kP2Hash = CAP, kP3Items = CAP / kP3Threads, kP3Ent = CAP / kP3Threads;
@@ -1572,7 +1601,7 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
     for (int k = 0; k < kP3Items; ++k)
       if (dj[k] >= 0) { d_key[dj[k]] = ky[k]; d_zw[dj[k]] = make_int2((int)rc[k].z, (int)rc[k].w); }
     __syncthreads();
-    part_evict<kP2Hash>(a, nd, (int64_t)p * kPartCap, d_rec, d_ent, d_base, s_lock, s_late, h_slot, h_cnt, tbl, tp0, rowb, s0, d_key, d_zw,
+    part_evict<kP2Hash, short, kP3Threads, kW>(a, nd, (int64_t)p * kPartCap, d_rec, d_ent, d_base, s_lock, s_late, h_slot, h_cnt, tbl, tp0, rowb, s0, d_key, d_zw,
 #ifdef P3_NO_FRESH
                         nullptr
 #else
@@ -1997,6 +2026,35 @@ static thread_local int t_rerun_epoch = 0;
 static thread_local int t_stage = 0;
 static thread_local uint64_t t_protect = ~0ull;
 void mi355i_fused_stage(int stage, uint64_t protect) { t_stage = stage; t_protect = protect; }
+// per-key frequency weights bound by mi355_demb_bind_weights for the next index stage of this thread (nullptr: none)
+static thread_local const int64_t* t_wts = nullptr;
+static thread_local int64_t t_wts_n = 0;
+static thread_local void* t_wts_ws = nullptr;
+static thread_local int64_t t_wts_ws_bytes = 0;
+const int64_t* mi355i_take_weights(int64_t* num_keys, void** workspace, int64_t* workspace_bytes) {
+  const int64_t* w = t_wts;
+  if (num_keys) *num_keys = t_wts_n;
+  if (workspace) *workspace = t_wts_ws;
+  if (workspace_bytes) *workspace_bytes = t_wts_ws_bytes;
+  t_wts = nullptr; t_wts_n = 0; t_wts_ws = nullptr; t_wts_ws_bytes = 0;
+  return w;
+}
+
+
+// Binds per-key frequency weights (int64 [num_keys], one per key of the batch, device memory) to the NEXT index stage this thread
+// issues -- mi355_demb_forward, mi355_demb_forward_fused, mi355_demb_forward_fused_rerun, mi355_demb_plan_forward / _stage / _rerun
+// --, which consumes the binding (a call that returns before it launched anything, MI355_ENOSPC of the plan calls, keeps it).
+// A counting score policy (Accumulate, LRU_LFU's frequency word) and the insert of a new key add the sum of a key's weights where
+// they add its occurrence count otherwise; outputs, gradients and the other policies do not see them, nor does an eval forward.
+// Negative weights are the caller's error (not checked).  workspace: mi355_demb_weights_workspace_bytes(num_keys, num_tables) bytes
+// of scratch, untouched until that call's kernels have run.
+int mi355_demb_bind_weights(const int64_t* weights, int64_t num_keys, void* workspace, int64_t workspace_bytes) {
+  t_wts = nullptr;
+  MI355_CHECK_ARG(num_keys >= 0 && (weights || num_keys == 0), "bind weights: null weights");
+  MI355_CHECK_ARG(workspace || workspace_bytes == 0, "bind weights: null workspace");
+  t_wts = weights; t_wts_n = num_keys; t_wts_ws = workspace; t_wts_ws_bytes = workspace_bytes;
+  return MI355_OK;
+}
 
 // Has the forward with this epoch flooded a partition's record list?  0: no (its CSR is complete), 1: yes (re-run its index stage
 // with mi355_demb_forward_fused_rerun / mi355_demb_plan_rerun before its backward), -1: not known within wait_ms milliseconds
@@ -2045,6 +2103,12 @@ static inline int part_count(int64_t n, int64_t num_tables) {
 }
 
 // slot-range partitions the fused forward would use for this batch / table (0: the per-slot-counter path)
+// scratch of mi355_demb_bind_weights: the weight sum of every deferred key (path (b)) and of every record (path (c))
+int64_t mi355_demb_weights_workspace_bytes(int64_t num_keys, int64_t num_tables) {
+  const int P = part_count(num_keys, num_tables);
+  return al256(8 * num_keys) + (P ? al256(8 * (int64_t)P * kPartCap) : 0);
+}
+
 int mi355_demb_forward_fused_partitions(int64_t n, int64_t num_tables, int64_t num_buckets) {
   const int P = part_count(n, num_tables);
   return (P > 0 && num_buckets >= 8 * (int64_t)P) ? P : 0;
@@ -2076,6 +2140,14 @@ int mi355_demb_forward_fused(
     /* CSR of the backward */ void* backward_workspace, int64_t backward_workspace_bytes, int use_side_stream,
     int* join_token,
     /* scratch */ void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  int64_t wts_n = 0, wts_ws_bytes = 0;
+  void* wts_ws = nullptr;
+  const int64_t* wts = mi355i_take_weights(&wts_n, &wts_ws, &wts_ws_bytes);   // (mi355_demb_bind_weights; eval ignores them)
+  if (!train) wts = nullptr;
+  if (wts) {
+    MI355_CHECK_ARG(wts_n == num_keys, "fused forward: bound weights are not one per key");
+    MI355_CHECK_ARG(wts_ws && wts_ws_bytes >= mi355_demb_weights_workspace_bytes(num_keys, num_tables), "fused forward: weights workspace too small");
+  }
   MI355_CHECK_ARG(workspace && workspace_bytes >= mi355_demb_forward_fused_workspace_bytes(num_keys, num_tables), "workspace too small");
   MI355_CHECK_ARG(num_tables >= 1 && num_tables <= kFusedMaxT, "fused forward: too many tables");
   MI355_CHECK_ARG(bucket_capacity > 0 && bucket_capacity % 16 == 0, "bucket capacity must be a positive multiple of 16");
@@ -2124,6 +2196,12 @@ int mi355_demb_forward_fused(
   a.protect = t_protect;
   a.cap = kPartCap; a.part_ready = nullptr;
   a.magic0 = num_buckets > 0 ? ~0ull / (uint64_t)num_buckets : 0ull;   // (one table: its buckets are all the buckets)
+  a.wts = wts; a.rec_w = nullptr; a.d_w = nullptr;
+  if (wts) {
+    uint8_t* ww = (uint8_t*)wts_ws;
+    a.d_w = (int64_t*)ww; ww += al256(8 * n);
+    if (train && part_count(n, num_tables)) a.rec_w = (int64_t*)ww;
+  }
   {
     const int P = train ? part_count(n, num_tables) : 0;
     if (P > 0 && num_buckets >= 8 * (int64_t)P) {
@@ -2283,7 +2361,9 @@ int mi355_demb_forward_fused(
 #define LAUNCH_PROBE(TILE, THREADS)                                                                                        \
   do {                                                                                                                     \
     const unsigned grid = (unsigned)ceil_div(n, TILE);                                                                     \
-    if (train) hipLaunchKernelGGL((fused_probe_kernel<TILE, THREADS, true>), dim3(grid), dim3(THREADS), 0, stream, a);    \
+    if (train && wts) hipLaunchKernelGGL((fused_probe_kernel<TILE, THREADS, true, false, false, false, false, false, true>), dim3(grid), \
+                                         dim3(THREADS), 0, stream, a);                                                          \
+    else if (train) hipLaunchKernelGGL((fused_probe_kernel<TILE, THREADS, true>), dim3(grid), dim3(THREADS), 0, stream, a); \
     else hipLaunchKernelGGL((fused_probe_kernel<TILE, THREADS, false>), dim3(grid), dim3(THREADS), 0, stream, a);         \
   } while (0)
     if (part) {
@@ -2306,27 +2386,34 @@ int mi355_demb_forward_fused(
         if (tlen > cap) tlen = cap;
         if (tlen < 256) tlen = 256;
         a.tl = (int)tlen;
-#define LAUNCH_PC(TILE, THREADS, WPS)                                                                                                   \
+#define LAUNCH_PC(TILE, THREADS, WPS, W)                                                                                                \
   do {                                                                                                                                   \
     const dim3 grid((unsigned)ceil_div(n, tlen)), blk(THREADS);                                                                          \
-    if (a.mt && seq) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, true, true>), grid, blk, 0, stream, a);                     \
-    else if (a.mt) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, true, false>), grid, blk, 0, stream, a);                      \
-    else if (seq) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, false, true>), grid, blk, 0, stream, a);                       \
-    else hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, false, false>), grid, blk, 0, stream, a);                               \
+    if (a.mt && seq) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, true, true, W>), grid, blk, 0, stream, a);                  \
+    else if (a.mt) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, true, false, W>), grid, blk, 0, stream, a);                   \
+    else if (seq) hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, false, true, W>), grid, blk, 0, stream, a);                    \
+    else hipLaunchKernelGGL((probe_c_kernel<TILE, THREADS, WPS, false, false, W>), grid, blk, 0, stream, a);                            \
   } while (0)
-        if (cap == 2048) LAUNCH_PC(2048, 1024, 4);
-        else LAUNCH_PC(1024, 1024, 4);      // (one block per CU by construction: the register budget of four waves per SIMD)
+        if (wts) {
+          if (cap == 2048) LAUNCH_PC(2048, 1024, 4, true);
+          else LAUNCH_PC(1024, 1024, 4, true);
+        } else if (cap == 2048) LAUNCH_PC(2048, 1024, 4, false);
+        else LAUNCH_PC(1024, 1024, 4, false);      // (one block per CU by construction: the register budget of four waves per SIMD)
         (void)0;
 #undef LAUNCH_PC
       } else {
-#define LAUNCH_C(MT, SEQ) hipLaunchKernelGGL((fused_probe_kernel<2048, 1024, true, true, false, true, MT, SEQ>), dim3((unsigned)ceil_div(n, 2048)), dim3(1024), 0, stream, a)
+#define LAUNCH_C(MT, SEQ, W) hipLaunchKernelGGL((fused_probe_kernel<2048, 1024, true, true, false, true, MT, SEQ, W>), dim3((unsigned)ceil_div(n, 2048)), dim3(1024), 0, stream, a)
         // (bucket capacities that are not a power of two: the round-3 probe kernel with the generic bucket arithmetic)
-        const int v = (a.mt ? 2 : 0) | (seq ? 1 : 0);
+        const int v = (a.mt ? 2 : 0) | (seq ? 1 : 0) | (wts ? 4 : 0);
         switch (v) {
-          case 0: LAUNCH_C(false, false); break;
-          case 1: LAUNCH_C(false, true); break;
-          case 2: LAUNCH_C(true, false); break;
-          default: LAUNCH_C(true, true); break;
+          case 0: LAUNCH_C(false, false, false); break;
+          case 1: LAUNCH_C(false, true, false); break;
+          case 2: LAUNCH_C(true, false, false); break;
+          case 3: LAUNCH_C(true, true, false); break;
+          case 4: LAUNCH_C(false, false, true); break;
+          case 5: LAUNCH_C(false, true, true); break;
+          case 6: LAUNCH_C(true, false, true); break;
+          default: LAUNCH_C(true, true, true); break;
         }
 #undef LAUNCH_C
       }
@@ -2353,6 +2440,7 @@ int mi355_demb_forward_fused(
     if (rerun_only) goto rerun_chain;      // (a flooded step: its forward ran, only the index stage is redone)
     if (part_fused) { late.ready = a.part_ready; late.cap = kPartCap; late.notice = a.notice; }
     else if (stage == 2) { }               // (the partition kernel ran with the step's index stage)
+    else if (wts) hipLaunchKernelGGL((fused_part3_kernel<kPartCap, true>), dim3((unsigned)a.P), dim3(kP3Threads), 0, stream, a, o, bptr, bcsr, hot);
     else hipLaunchKernelGGL(fused_part3_kernel<kPartCap>, dim3((unsigned)a.P), dim3(kP3Threads), 0, stream, a, o, bptr, bcsr, hot);
     MI355_LAUNCH_CHECK();
     if (stage == 1) goto rerun_chain;      // index stage only: the gather follows in a stage-2 call
@@ -2362,7 +2450,9 @@ int mi355_demb_forward_fused(
       const unsigned grid = (unsigned)ceil_div(n, 256);
 #define LAUNCH_RG(S, D)                                                                                                                \
   do {                                                                                                                                 \
-    if (part_fused) hipLaunchKernelGGL((gather_rows_part_kernel<S, D>), dim3((grid + 1) / 2 + (unsigned)a.P), dim3(kP3lThreads), 0, stream, a, o, bptr,  \
+    if (part_fused && wts) hipLaunchKernelGGL((gather_rows_part_kernel<S, D, true>), dim3((grid + 1) / 2 + (unsigned)a.P), dim3(kP3lThreads), 0,   \
+                                              stream, a, o, bptr, bcsr, hot, a.occ_addr, late, n, (int)emb_dim, out, emb_dim, lg);        \
+    else if (part_fused) hipLaunchKernelGGL((gather_rows_part_kernel<S, D>), dim3((grid + 1) / 2 + (unsigned)a.P), dim3(kP3lThreads), 0, stream, a, o, bptr,  \
                                        bcsr, hot, a.occ_addr, late, n, (int)emb_dim, out, emb_dim, lg);                                \
     else hipLaunchKernelGGL((gather_rows_late_kernel<S, D>), dim3(grid), dim3(256), 0, stream, a.occ_addr, late, n, (int)emb_dim, out, \
                             emb_dim, lg);                                                                                              \
@@ -2392,7 +2482,8 @@ int mi355_demb_forward_fused(
       // the chain of the per-slot-counter path over the same buffers, gated on this call's epoch: probe (keys already inserted are
       // found), numbering, CSR scatter (eager reverse indices); the pooled output above is complete either way.  The first pass
       // inserted and scored every key of the step -- only its bookkeeping flooded -- so the re-probe must not count them again:
-      // Assign / timer scores are idempotent, a counting find policy drops its count (LFU scores once per step)
+      // Assign / timer scores are idempotent, a counting find policy drops its count (LFU scores once per step) -- and with per-key
+      // weights their sum, the same way; a key the re-run inserts (its record was lost to the flood) is assigned its weight sum
       FusedArgs b = a;
       if (b.find_policy == kAccumulate) b.find_policy = kConst;
       else if (b.find_policy == kLruLfu) b.find_policy = kGlobalTimer;
@@ -2400,7 +2491,9 @@ int mi355_demb_forward_fused(
       b.mt = 0; b.ptab = nullptr; b.rerun_mark = nullptr;
       b.notice = nullptr;
       if (!rerun_only) { b.gate = a.hdr + 6; b.gate_val = epoch; }      // in line: gated on this call's epoch; re-run: the host knows
-      hipLaunchKernelGGL((fused_probe_kernel<2048, 1024, true>), dim3((unsigned)ceil_div(n, 2048)), dim3(1024), 0, stream, b);
+      if (wts) hipLaunchKernelGGL((fused_probe_kernel<2048, 1024, true, false, false, false, false, false, true>), dim3((unsigned)ceil_div(n, 2048)),
+                                  dim3(1024), 0, stream, b);
+      else hipLaunchKernelGGL((fused_probe_kernel<2048, 1024, true>), dim3((unsigned)ceil_div(n, 2048)), dim3(1024), 0, stream, b);
       static int ncu_r = 0;
       if (!ncu_r) {
         int dev = 0;
@@ -2408,7 +2501,8 @@ int mi355_demb_forward_fused(
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu_r = prop.multiProcessorCount;
         if (ncu_r <= 0) ncu_r = 64;
       }
-      hipLaunchKernelGGL(fused_mid_kernel<true>, dim3((unsigned)ceil_div(n, kScanTile)), dim3(kScanThreads), 0, stream, b, o, bptr, hot, true, ncu_r);
+      if (wts) hipLaunchKernelGGL((fused_mid_kernel<true, true>), dim3((unsigned)ceil_div(n, kScanTile)), dim3(kScanThreads), 0, stream, b, o, bptr, hot, true, ncu_r);
+      else hipLaunchKernelGGL(fused_mid_kernel<true>, dim3((unsigned)ceil_div(n, kScanTile)), dim3(kScanThreads), 0, stream, b, o, bptr, hot, true, ncu_r);
       MI355_LAUNCH_CHECK();
       STEP(mi355i_csr_from_slots(csr_rank, b.occ_slot, b.occ + 1, reverse_indices, n, combiner >= 0 ? offsets : nullptr, num_bags,
                                  bptr, bcsr, hot_ws, hot_bytes_, emb_dim, a.hdr, nullptr, stream, b.gate, epoch, a.rerun_mark));
@@ -2462,10 +2556,12 @@ int mi355_demb_forward_fused(
     HotList hot{};
     if (hot_ws) hot = hot_carve(hot_ws, n, emb_dim);
     if (ntile <= kSelfPrefixMaxTiles) {
-      hipLaunchKernelGGL(fused_mid_kernel<true>, dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
+      if (wts) hipLaunchKernelGGL((fused_mid_kernel<true, true>), dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
+      else hipLaunchKernelGGL(fused_mid_kernel<true>, dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
     } else {
       hipLaunchKernelGGL(fused_scan_partials_kernel, dim3(1), dim3(kScanThreads), 0, cs, a.partial, ntile);
-      hipLaunchKernelGGL(fused_mid_kernel<false>, dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
+      if (wts) hipLaunchKernelGGL((fused_mid_kernel<false, true>), dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
+      else hipLaunchKernelGGL(fused_mid_kernel<false>, dim3((unsigned)ntile), dim3(kScanThreads), 0, cs, a, o, bptr, hot, hot_ws != nullptr, ncu);
     }
     MI355_LAUNCH_CHECK();
     STEP(mi355i_csr_from_slots(csr_rank, a.occ_slot, a.occ + 1, reverse_indices, n, combiner >= 0 ? offsets : nullptr, num_bags,

@@ -75,6 +75,8 @@ int mi355i_backward_fused(const int32_t* ptr, const int32_t* csr_src, int64_t nu
 // stage (0 whole forward, 1 index stage only, 2 gather only) and eviction limit of the NEXT mi355_demb_forward_fused call of this
 // thread (fused_fwd.hip; mi355_demb_plan_stage brackets its call with it)
 void mi355i_fused_stage(int stage, uint64_t protect);
+// the weights bound by mi355_demb_bind_weights (nullptr: none), handed over and cleared
+const int64_t* mi355i_take_weights(int64_t* num_keys, void** workspace, int64_t* workspace_bytes);
 
 // bench.py's live kernel timing (err.hip): event of slot (0 gather, 1 backward kernel), end 0 / 1
 void mi355i_prof_mark(int slot, int end, hipStream_t stream);

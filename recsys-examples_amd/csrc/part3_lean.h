@@ -28,7 +28,7 @@ namespace mi355 {
 
 constexpr int kP3lThreads = 512;
 
-template <int CAP>
+template <int CAP, bool kW = false>
 __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* __restrict__ ptr, int* __restrict__ csr_src, const HotList& hot,
                                            int p) {
   constexpr int HASH = CAP, T = kP3lThreads, kEnt = HASH / T, kSubCapL = CAP / kPartSub, kDefMax = CAP / 4;
@@ -112,7 +112,7 @@ __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* 
   QST(3);
   const int nd = s_nd < kDefMax ? s_nd : kDefMax;
   if (nd > 0) {      // (block uniform)
-    part_evict<HASH, int, T>(a, nd, rec_base, d_rec, d_ent, d_base, s_lock, s_late, h_slot, h_cnt, tbl, tp0, rowb, s0, nullptr, nullptr, s_fresh);
+    part_evict<HASH, int, T, kW>(a, nd, rec_base, d_rec, d_ent, d_base, s_lock, s_late, h_slot, h_cnt, tbl, tp0, rowb, s0, nullptr, nullptr, s_fresh);
     __syncthreads();
     for (int e = tid; e < nd; e += T) {
       // the first record (rank base 0) of an entry created by the eviction owns the unique row's key
@@ -266,11 +266,11 @@ __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* 
 // (the POOLED gather with the partition blocks in front was measured a loss at C2 -- 0.1227 -> 0.1288 ms, profiles/r05_part_fused.txt --
 //  and removed in round 6: pooled batches keep the partition kernel of their own)
 // the sequence gather of path (c) with the partition blocks in front
-template <int SDT, int DDT>
+template <int SDT, int DDT, bool kW = false>   // kW: weighted records (part3_lean / part_evict)
 __global__ void __launch_bounds__(kP3lThreads, 8)
 gather_rows_part_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restrict__ csr_src, HotList hot,
                         const int64_t* __restrict__ occ_addr, LateRefs late, int64_t n, int D, void* dst, int64_t dst_stride, int lpr_log2) {
-  if ((int)blockIdx.x < a.P) { part3_lean<kPartCap>(a, o, ptr, csr_src, hot, (int)blockIdx.x); return; }
+  if ((int)blockIdx.x < a.P) { part3_lean<kPartCap, kW>(a, o, ptr, csr_src, hot, (int)blockIdx.x); return; }
   const int64_t bid = (int64_t)blockIdx.x - a.P;
   const int64_t i0 = (bid * (kP3lThreads >> 6) + (threadIdx.x >> 6)) * 64;
   if (i0 >= n) return;

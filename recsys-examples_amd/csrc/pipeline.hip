@@ -55,6 +55,12 @@ int mi355_demb_forward(
        early CSR was started.  NULL: the early CSR is joined on `stream` before this call returns. */
     int* join_token,
     /* scratch */ void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  // per-key frequency weights (mi355_demb_bind_weights): the unique stage sums them per key into `freq`, which is what a counting
+  // score policy adds / assigns below (reference: segmented_unique with frequency_counters); eval ignores them
+  int64_t wts_n = 0;
+  const int64_t* wts = mi355i_take_weights(&wts_n, nullptr, nullptr);
+  if (!train || !freq) wts = nullptr;
+  MI355_CHECK_ARG(!wts || wts_n == num_keys, "forward: bound weights are not one per key");
   MI355_CHECK_ARG(counter || !train, "a training forward needs the ref-counter array (found slots are pinned across the insert)");
   MI355_CHECK_ARG(workspace && workspace_bytes >= mi355_demb_forward_workspace_bytes(num_keys, num_tables),
                   "workspace too small");
@@ -72,7 +78,7 @@ int mi355_demb_forward(
 #define STEP(call) do { rc = (call); if (rc != MI355_OK) return rc; } while (0)
   // table ranges, dedup, table ids of the unique keys: one call, no separate range / memset / expand launches
   { mi355::RoctxRange rr("op:segmented_unique");
-  STEP(mi355i_segmented_unique(keys, num_keys, nullptr, num_tables, nullptr, freq ? 1 : 0, unique_keys, reverse_indices,
+  STEP(mi355i_segmented_unique(keys, num_keys, nullptr, num_tables, wts, freq ? 1 : 0, unique_keys, reverse_indices,
                                unique_offsets, freq, csr_cnt, csr_rank, offsets, feature_offsets, num_bags, table_range,
                                table_ids, uws, uws_bytes, stream)); }
   if (backward_workspace && train && csr_cnt && csr_rank && num_keys > 0 && combiner != -2) {

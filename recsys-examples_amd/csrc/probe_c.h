@@ -35,7 +35,9 @@
 
 namespace mi355 {
 
-template <int TILE, int THREADS, int WPS, bool kMT, bool kSeq>
+// kW: per-key frequency weights (FusedArgs::wts) -- an int64 weight sum per dedup entry next to s_cnt, which stays the occurrence
+// count (the CSR and the records need it); the sum is what the score policy adds and what the records hand to the partition kernel
+template <int TILE, int THREADS, int WPS, bool kMT, bool kSeq, bool kW = false>
 __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
   constexpr int PER = TILE / THREADS;
   constexpr int HASH = 2 * TILE;
@@ -46,6 +48,7 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
   __shared__ uint64_t s_key[TILE];
   __shared__ int s_tab[HASH];          // dedup: tile position of the key's representative; after the probe: (partition << 12) | position
   __shared__ int s_cnt[HASH];          // dedup: occurrences inside the tile; after the probe: slot code of the key's record
+  __shared__ int64_t s_w[kW ? HASH : 1];   // (kW) dedup: weight sum of the key's occurrences inside the tile
   __shared__ uint16_t s_sm[HASH];      // per dedup entry: start of the key's list in the tile | multi flag << 15
   __shared__ int s_bag[kSeq ? 1 : TILE];
   __shared__ int s_hist[kPartMax];     // records of this tile per partition, then their base in the partition's list
@@ -71,10 +74,12 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
   if (!a.timer) a.timer = device_clock();
   // ---- phase 0: everything that depends on nothing goes out first
   uint64_t kreg[PER];
+  int64_t wreg[kW ? PER : 1];
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const int64_t i = tile0 + q * THREADS + tid;
     kreg[q] = a.keys[i < a.n ? i : a.n - 1];
+    if constexpr (kW) wreg[q] = a.wts[i < a.n ? i : a.n - 1];
   }
   // the guessed bag window [wlo, wlo + WIN): bag of a position ~ position * bags / keys; thread t takes the bags wlo + t and
   // wlo + THREADS + t
@@ -132,7 +137,7 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
       if (wd < nw) a.tstat[wd] = 0ull;
     }
   }
-  for (int s = tid; s < HASH; s += THREADS) { s_tab[s] = -1; s_cnt[s] = 0; }
+  for (int s = tid; s < HASH; s += THREADS) { s_tab[s] = -1; s_cnt[s] = 0; if constexpr (kW) s_w[s] = 0; }
   for (int p = tid; p < a.P; p += THREADS) s_hist[p] = 0;
   if constexpr (!kSeq) for (int k = tid; k < TILE; k += THREADS) s_bag[k] = -1;
   if (tid == 0) s_cover = 1;
@@ -301,6 +306,7 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
       }
       hh[q] = h;
       rk[q] = atomicAdd(&s_cnt[h], 1);
+      if constexpr (kW) atomicAdd((unsigned long long*)&s_w[h], (unsigned long long)wreg[q]);
       if constexpr (!kMT) { if (claimed) lpq[q] = pkq[q] * 4096 + atomicAdd(&s_hist[pkq[q]], 1); }
     }
   }
@@ -404,11 +410,15 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
         int slot;
         const int gpos = s_pos[q * THREADS + tid];
         if (gpos >= 0) slot = (((int)hq[q] & Cm) & ~15) + gpos;
+        else if constexpr (kW) slot = thread_probe<true>(a, b, key, hq[q], s_w[hh[q]], inserted);
         else slot = thread_probe<true>(a, b, key, hq[q], cnt, inserted);
         if (slot >= 0) {
           gslot = (int)(b * a.t.C + slot);
           // (Assign / timer scores are the same value from every tile: plain stores)
-          if (!inserted) score_found(a, a.t.scores(b) + (int64_t)slot * a.t.ns, cnt);
+          if (!inserted) {
+            if constexpr (kW) score_found(a, a.t.scores(b) + (int64_t)slot * a.t.ns, s_w[hh[q]]);
+            else score_found(a, a.t.scores(b) + (int64_t)slot * a.t.ns, cnt);
+          }
         } else if (slot == -2) {
           defer = true;
         }
@@ -451,9 +461,10 @@ __global__ void __launch_bounds__(THREADS, WPS) probe_c_kernel(FusedArgs a) {
     int bag;
     if constexpr (kSeq) bag = (int)i; else bag = s_bag[li];
     if (isrep[q]) {
-      if (ref >= 0)
+      if (ref >= 0) {
         a.rec[ref] = make_uint4((uint32_t)i, (uint32_t)((sm & 0x8000) ? (int)tile0 + (sm & 0x7fff) : bag), (uint32_t)g, (uint32_t)cnt_tile[q]);
-      else
+        if constexpr (kW) a.rec_w[ref] = s_w[hh[q]];
+      } else
         a.hdr[a.ovf_word] = a.ovf_val;   // a partition received more records than it can hold: the step is flagged (see the module)
     }
     a.occ_slot[i] = ref;

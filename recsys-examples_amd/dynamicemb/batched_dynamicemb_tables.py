@@ -64,7 +64,7 @@ class _StepCtx:
 
     __slots__ = ("rev", "uoff", "tids", "slots", "row_addr", "offsets", "num_keys", "batch_size", "num_bags", "csr_cnt",
                  "csr_rank", "pinned", "event", "indices", "bwd_ws", "ring", "token", "tier_pins", "fwd_addr", "scratch",
-                 "pin_cell", "__weakref__")
+                 "pin_cell", "wts", "wts_ws", "__weakref__")
 
     def release_ring(self):
         """hand the early-CSR ring slot back (after the backward, or when the step is dropped without one)"""
@@ -479,6 +479,51 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             return P.ACCUMULATE, None, P.ASSIGN, None, True
         return P.LRU_LFU, None, P.LRU_LFU, None, True
 
+    # ---------------------------------------------------------------------------------- per-key frequency weights
+    # The reference's per_sample_weights (forward) / frequency_counters (prefetch) are COUNTS, not pooling weights
+    # (BatchedDynamicEmbeddingTablesV2.forward -> prefetch(..., frequency_counters), batched_dynamicemb_tables.py:1061; summed per
+    # unique key by segmented_unique, batched_dynamicemb_function.py:74-159): an LFU score, LRU_LFU's frequency word and the
+    # admission counter grow by the sum of a key's weights instead of its occurrences.  Outputs and gradients never see them.
+    def _check_weights(self, w, indices: torch.Tensor) -> torch.Tensor:
+        """shape / dtype / device only (no host read: the plan and the staged step stay capturable); negative weights are the
+        caller's error, as in the reference"""
+        if not isinstance(w, torch.Tensor):
+            raise TypeError("per_sample_weights must be a tensor")
+        if w.dim() != 1 or w.numel() != indices.numel():
+            raise ValueError(f"per_sample_weights must be 1-D with one entry per key ({indices.numel()}), got shape {tuple(w.shape)}")
+        if w.device != indices.device:
+            raise ValueError(f"per_sample_weights is on {w.device}, the keys on {indices.device}")
+        if w.is_complex():
+            raise TypeError("per_sample_weights must be real or integer")
+        return w.long().contiguous()      # (truncation, as the reference's .long())
+
+    def _with_weights(self, w, fn, *args, **kwargs):
+        """runs fn with the step's weights visible to every index path (self._wts), then clears them"""
+        prev = self.__dict__.get("_wts")
+        object.__setattr__(self, "_wts", w)
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            object.__setattr__(self, "_wts", prev)
+
+    def _bind_weights(self, n: int):
+        """binds this step's weights to the next native index stage (mi355_demb_bind_weights) -> (weights, scratch) to keep alive
+        with the step, or (None, None)"""
+        w = self.__dict__.get("_wts")
+        if w is None:
+            return None, None
+        L = lib()
+        ws = torch.empty(max(int(L.mi355_demb_weights_workspace_bytes(n, self.num_tables)), 256), dtype=torch.uint8, device=self.device_)
+        check(L.mi355_demb_bind_weights(w.data_ptr(), n, ws.data_ptr(), ws.numel()), "demb_bind_weights")
+        return w, ws
+
+    def _unique_csr(self, indices, rng, T, train: bool):
+        """segmented_unique_csr (+ the weight sum of every unique key when the step has weights; else None)"""
+        w = self.__dict__.get("_wts") if train else None
+        if w is None:
+            return (*ext.segmented_unique_csr(indices, rng, T), None)
+        return ext.segmented_unique_csr_weighted(indices, rng, T, w)
+
     # ---------------------------------------------------------------------------------- forward
     def _forward_impl(self, indices: torch.Tensor, offsets: torch.Tensor, train: bool, prefetch_only: bool = False):
         if (train and self._plan_ok and not prefetch_only and not self._pin and not self._prefetch_states and not self._orphan_pins
@@ -568,6 +613,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
                 st.ring = (self._bwd_busy, slot)
                 st.bwd_ws = buf
         tok = ctypes.c_int(-1)
+        st.wts, st.wts_ws = self._bind_weights(n) if train else (None, None)
         check(lib().mi355_demb_forward(
             ptr(tb.table_storage_), ptr(tb.table_bucket_offsets_), tb.bucket_capacity_, tb.num_scores_,
             ptr(tb.bucket_sizes), ptr(tb._ref_counter), tb._ref_counter.numel(),
@@ -803,6 +849,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             out = torch.empty(n, self.dims[0], dtype=self.output_dtype, device=self.device_)
         sval = self._step if self._plan_step_score else (self._custom_score if self._plan_custom_score else 0)
         s_ = _raw_stream(_cur_device())
+        wts, wts_ws = self._bind_weights(n)
         rc = 1
         if not self._pf_c_used:
             if buf is not None:
@@ -827,6 +874,8 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
                 ring[0][ring[1]] = False
             check(rc, "demb_plan_forward")
         st = _PlanStep(self, buf, n, self.num_tables, ring, offsets, B, num_bags)
+        if wts is not None:
+            st.wts, st.wts_ws = wts, wts_ws
         if score is not None:
             self._inflight[st] = score
         tok = self._plan_state.value
@@ -910,6 +959,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             return None                  # (more steps outstanding than the ring holds: the caller's stream-managed prefetch)
         self._pf_c_used = True
         cur = _raw_stream(_cur_device())
+        wts, wts_ws = self._bind_weights(n)
         if side is None:
             buf, rc = self._plan_stage_call(plan, 1, indices, n, offsets, num_bags, B, sval, timer, None, buf, ring, cur)
         else:
@@ -922,7 +972,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             if ring is not None:
                 ring[0][ring[1]] = False
             if rc == 3:          # nothing was launched: not eligible after all (long bags, fp16 rows ...)
-                return None
+                return None      # (the binding of the weights was consumed: the pinning prefetch binds them again)
             check(rc, "demb_plan_stage")
         st = _PlanStep(self, buf, n, self.num_tables, ring, offsets, B, num_bags)
         tok = self._plan_state.value
@@ -930,6 +980,11 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
         st.epoch = -2 - tok if tok < -2 else 0
         st.indices, st.sval, st.timer = indices, sval, timer
         st.staged = True
+        if wts is not None:
+            st.wts, st.wts_ws = wts, wts_ws
+            if side is not None:     # (allocated on the current stream, read on the prefetch stream)
+                wts.record_stream(side)
+                wts_ws.record_stream(side)
         st.ev_slot = ring[1] if side is not None else -1
         st.prepared = 1 if n > 0 else 0
         self._inflight[st] = score
@@ -1043,6 +1098,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             st.p("rev"), st.p("uoff"), st.p("tids"), st.p("slots"), st.p("row_addr"), st.p("freq") if need_freq else None,
             st.p("csr_cnt"), st.p("csr_rank"), st.p("bwd_ws") if bwd_b else None, bwd_b, use_side)
         tail = (st.p("fwd_ws"), fwd_b)
+        st.wts, st.wts_ws = self._bind_weights(n) if train else (None, None)
         check(L.mi355_demb_forward_fused(*head, ctypes.byref(tok), *tail, stream()), "demb_forward_fused")
         st.lazy = tok.value <= -2
         if tok.value < -2:       # path (c): the step's overflow notice is read before its CSR is used (_FusedStep.settle)
@@ -1062,6 +1118,9 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
         its index stage is redone on the per-slot-counter path over the step's own buffers (csrc/fused_fwd.hip:
         mi355_demb_forward_fused_rerun); the forward's output stands, the backward that follows updates every row"""
         self.overflow_reruns = getattr(self, "overflow_reruns", 0) + 1
+        wts = getattr(st, "wts", None)
+        if wts is not None:      # (the re-run scores nothing it found; a key it inserts is assigned its weight sum)
+            check(lib().mi355_demb_bind_weights(wts.data_ptr(), st.num_keys, st.wts_ws.data_ptr(), st.wts_ws.numel()), "demb_bind_weights")
         if getattr(st, "plan_step", False):
             buf = st.buf
             check(lib().mi355_demb_plan_rerun(self._plan, st.indices.data_ptr(), st.num_keys, st.offsets.data_ptr(), st.num_bags,
@@ -1146,7 +1205,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             out = torch.empty(n, self.dims[0], dtype=self.output_dtype, device=dev)
             combiner = -1
         rng = ext.get_table_range(offsets, self.feature_offsets)
-        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank = ext.segmented_unique_csr(indices, rng, T)
+        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank, wsum = self._unique_csr(indices, rng, T, train)
         nu = int(st.uoff[-1].item())
         st.row_addr = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
         fwd_addr, scratch = st.row_addr, None      # (admission: the forward also reads scratch rows the backward must not touch)
@@ -1155,8 +1214,9 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             uk = ukeys[:nu].contiguous()
             tids = ext.expand_table_ids_cuda(st.uoff, nu)
             fp, fs, ip, isc, need_freq = self._scores(nu)
+            freq = wsum[:nu] if wsum is not None else st.csr_cnt[:nu].to(torch.int64)   # occurrences (weights: their sums)
             if need_freq:
-                fs = isc = st.csr_cnt[:nu].to(torch.int64)
+                fs = isc = freq
             find = ScoreArg("score", None if fs is None else fs[:nu], fp)
             ins = ScoreArg("score", None if isc is None else isc[:nu], ip)
             addr = st.row_addr[:nu]
@@ -1178,7 +1238,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
                 rej = new[:0]
                 if admission and new.numel():
                     km, tm = uk[new].contiguous(), tids[new].contiguous()
-                    acc = self._admission_counter.add(km, tm, st.csr_cnt[:nu].to(torch.int64)[new].contiguous())
+                    acc = self._admission_counter.add(km, tm, freq[new].contiguous())
                     admit = self._admit_strategy.admit(km, acc)
                     rej, new = new[~admit], new[admit]
                     if new.numel():
@@ -1391,7 +1451,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             out = torch.empty(n, self.dims[0], dtype=self.output_dtype, device=dev)
             combiner = -1
         rng = ext.get_table_range(offsets, self.feature_offsets)
-        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank = ext.segmented_unique_csr(indices, rng, T)
+        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank, wsum = self._unique_csr(indices, rng, T, True)
         nu = int(st.uoff[-1].item())
         st.row_addr = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)   # what the backward updates: stored rows only
         fwd_addr = st.row_addr
@@ -1400,7 +1460,8 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             uk = ukeys[:nu].contiguous()
             tids = ext.expand_table_ids_cuda(st.uoff, nu)
             fp, fs, ip, isc, need_freq = self._scores(nu)
-            freq = st.csr_cnt[:nu].to(torch.int64)       # occurrences of every unique key in this batch
+            # occurrences of every unique key in this batch (per-key frequency weights: the sum of its weights)
+            freq = wsum[:nu] if wsum is not None else st.csr_cnt[:nu].to(torch.int64)
             if need_freq:
                 fs = isc = freq
             find = ScoreArg("score", None if fs is None else fs[:nu], fp)
@@ -1474,7 +1535,13 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
         later batch (dedup, find, insert + first-touch init of unseen keys, pin) on the CURRENT stream, typically a side
         stream, while earlier batches still compute.  The rows it touches stay pinned (ref-counters) until the batch's
         backward releases them, so a later prefetch cannot evict them.  forward() consumes the states in FIFO order and
-        only gathers."""
+        only gathers.  frequency_counters: the per-key frequency weights of the batch (forward()'s per_sample_weights); the
+        later forward of the batch uses these."""
+        if frequency_counters is not None:
+            w = self._check_weights(frequency_counters, indices)
+            if not self.training:
+                return
+            return self._with_weights(w, self.prefetch, indices, offsets, forward_stream, batch_size_per_feature_per_rank)
         if not self.training:
             return
         st = None
@@ -1496,11 +1563,17 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
                 indices.record_stream(forward_stream)
         self._prefetch_states.append(st)
 
-    def prefetch_async(self, indices: torch.Tensor, offsets: torch.Tensor) -> None:
+    def prefetch_async(self, indices: torch.Tensor, offsets: torch.Tensor, per_sample_weights=None) -> None:
         """prefetch() on the module's own prefetch stream, ordered behind what the CURRENT stream holds at the call (the batch,
         and the backward whose rows must be final before an eviction may recycle one) -- the fork, the end-of-stage mark and the
         wait of the later forward are library-owned events, no stream context is switched on the host.  Call it where the
-        reference's pipeline calls prefetch: after forward(batch k) has been issued, before backward(batch k)."""
+        reference's pipeline calls prefetch: after forward(batch k) has been issued, before backward(batch k).
+        per_sample_weights: the batch's per-key frequency weights (forward()'s argument); its later forward uses these."""
+        if per_sample_weights is not None:
+            w = self._check_weights(per_sample_weights, indices)
+            if not self.training:
+                return
+            return self._with_weights(w, self.prefetch_async, indices, offsets)
         if not self.training:
             return
         side = self.__dict__.get("_pf_stream")
@@ -1603,10 +1676,15 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
 
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor, per_sample_weights=None,
                 feature_requires_grad=None, batch_size_per_feature_per_rank=None, total_unique_indices=None):
-        if per_sample_weights is not None:
-            raise NotImplementedError("per_sample_weights is not supported (nor by the reference's kernels)")
+        """per_sample_weights (optional, 1-D, one per key of `indices`, any real / integer dtype, truncated with .long()): per-key
+        FREQUENCY weights, as in the reference -- an LFU score (LRU_LFU: its frequency word) and the admission counter grow by the
+        sum of a key's weights in the step instead of its occurrence count; pooled sums / means, sequence rows and gradients are
+        not weighted, the other score strategies ignore them, and so does an eval forward (after the argument checks)."""
+        w = self._check_weights(per_sample_weights, indices) if per_sample_weights is not None else None
         if self.training and torch.is_grad_enabled():
-            return _LookupFunction.apply(self, indices, offsets, self._empty_tensor)
+            if w is None:
+                return _LookupFunction.apply(self, indices, offsets, self._empty_tensor)
+            return self._with_weights(w, _LookupFunction.apply, self, indices, offsets, self._empty_tensor)
         out, _ = self._forward_impl(indices, offsets, train=False)
         return out
 

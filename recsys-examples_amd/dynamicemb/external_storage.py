@@ -174,7 +174,11 @@ class ExternalStorageTables(BatchedDynamicEmbeddingTablesV2):
         pooled = self.pooling_mode != DynamicEmbPoolingMode.NONE
         lfu = self._score_strategy == DynamicEmbScoreStrategy.LFU
         seg = ext.get_table_range(offsets, self.feature_offsets)
-        _, ukeys, rev, uoff, freq = ext.segmented_unique_cuda(indices, seg, T, torch.empty(0, dtype=torch.int64, device=dev) if lfu else None)
+        # LFU: the store learns every unique key's occurrences -- with per-key frequency weights, the sum of its weights (the
+        # reference's frequency_counters) -- as lfu_accumulated_frequency
+        wts = self.__dict__.get("_wts") if train else None
+        fin = (wts if wts is not None else torch.empty(0, dtype=torch.int64, device=dev)) if lfu else None
+        _, ukeys, rev, uoff, freq = ext.segmented_unique_cuda(indices, seg, T, fin)
         nu = int(uoff[T].item())      # (the store is host code: its call is a synchronisation point anyway)
         ukeys = ukeys[:nu].contiguous()
         tids = ext.expand_table_ids_cuda(uoff, nu)
@@ -290,7 +294,7 @@ class ExternalStorageTables(BatchedDynamicEmbeddingTablesV2):
             out = torch.empty(n, self.dims[0], dtype=self.output_dtype, device=dev)
             combiner = -1
         rng = ext.get_table_range(offsets, self.feature_offsets)
-        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank = ext.segmented_unique_csr(indices, rng, T)
+        ukeys, st.rev, st.uoff, st.csr_cnt, st.csr_rank, wsum = self._unique_csr(indices, rng, T, train)
         nu = int(st.uoff[-1].item())
         st.row_addr = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
         keep = []          # buffers the row addresses point into (alive until the gather has been queued / the backward has run)
@@ -300,8 +304,9 @@ class ExternalStorageTables(BatchedDynamicEmbeddingTablesV2):
             uk = ukeys[:nu].contiguous()
             tids = ext.expand_table_ids_cuda(st.uoff, nu)
             fp, fs, ip, isc, need_freq = c._scores(nu)
+            freq = wsum[:nu] if wsum is not None else st.csr_cnt[:nu].to(torch.int64)   # occurrences (weights: their sums)
             if need_freq:
-                fs = isc = st.csr_cnt[:nu].to(torch.int64)
+                fs = isc = freq
             find = ScoreArg("score", None if fs is None else fs[:nu], fp)
             addr = st.row_addr[:nu]
             _, f0, s0 = c.table.lookup(uk, tids, find)
@@ -315,7 +320,7 @@ class ExternalStorageTables(BatchedDynamicEmbeddingTablesV2):
                 pins.append((hs, ht))
             if miss.numel():
                 k1, t1 = uk[miss].contiguous(), tids[miss].contiguous()
-                fr1 = st.csr_cnt[:nu].to(torch.int64)[miss].contiguous() if need_freq else None
+                fr1 = freq[miss].contiguous() if need_freq else None
                 if train:
                     nm, mkeys, midx, mtids, _, _, _, vals = _parse_find(self._storage.find(k1, t1, CopyMode.VALUE, fr1))
                     if vals.size(1) < self.max_V:

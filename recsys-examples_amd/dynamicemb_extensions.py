@@ -479,6 +479,25 @@ def segmented_unique_csr(keys, segmented_range, num_tables):
     return unique_keys, out_idx, table_offsets, cnt, rank
 
 
+def segmented_unique_csr_weighted(keys, segmented_range, num_tables, weights):
+    """segmented_unique_csr with per-key frequency weights (int64 [N]): -> (unique_keys, output_indices, table_offsets, csr_cnt,
+    csr_rank, weight sums i64[N]) -- the sum of every unique key's weights, where the counts stay occurrences (the reference's
+    segmented_unique with frequency_counters, batched_dynamicemb_function.py:74-159)."""
+    n = keys.numel()
+    dev = keys.device
+    unique_keys = torch.empty_like(keys)
+    out_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    table_offsets = torch.empty(num_tables + 1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    wsum = torch.empty(n, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().mi355_segmented_unique_workspace_bytes(n), dev)
+    check(lib().mi355_segmented_unique_csr(ptr(keys), n, ptr(segmented_range), num_tables, ptr(weights), 1, ptr(unique_keys),
+                                           ptr(out_idx), ptr(table_offsets), ptr(wsum), ptr(cnt), ptr(rank), ptr(ws), ws.numel(),
+                                           stream()), "segmented_unique_csr")
+    return unique_keys, out_idx, table_offsets, cnt, rank, wsum
+
+
 def group_by_unique_csr(csr_cnt, csr_rank, reverse_indices, num_unique_max, offsets=None, nu_dev=None, dim=0):
     """group_by_unique from the forward's counts / ranks: scan + scatter (no histogram, no atomics)."""
     n = reverse_indices.numel()

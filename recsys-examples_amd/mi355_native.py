@@ -126,6 +126,8 @@ _SIGS = {
     "mi355_demb_aux_numel": [c_i64, c_i64],
     "mi355_demb_forward_fused_workspace_bytes": [c_i64, c_i64],
     "mi355_demb_forward_fused_partitions": [c_i64, c_i64, c_i64],
+    "mi355_demb_weights_workspace_bytes": [c_i64, c_i64],
+    "mi355_demb_bind_weights": [c_p, c_i64, c_p, c_i64],
     "mi355_side_join": [c_int, c_p],
     "mi355_demb_fused_materialize": [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p],
     "mi355_profile_kernels": [c_int],
@@ -183,6 +185,7 @@ _SIGS = {
     "mi355_last_error": [],
 }
 _RESTYPES = {
+    "mi355_demb_weights_workspace_bytes": c_i64,
     "mi355_segmented_unique_workspace_bytes": c_i64,
     "mi355_group_by_unique_csr_workspace_bytes": c_i64,
     "mi355_table_export_batch_workspace_bytes": c_i64,
