@@ -1498,6 +1498,28 @@ __device__ __forceinline__ void publish_notice(const FusedArgs& a) {
   __hip_atomic_store(a.notice, (unsigned long long)(unsigned)a.ovf_val | (f << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// header, chunk tasks and zeroed accumulator of a chunked hot row (hot.h), by `stride` lanes (lane `l`) or one thread (0, 1)
+__device__ __forceinline__ void register_hot_row(const HotList& hot, int h, int uid, int pv, int c, int t0, int l, int stride) {
+  const int nch = (c + hot.kchunk - 1) / hot.kchunk;
+  if (l == 0) {
+    hot.hot_done[h] = 0;
+    hot.hot_nchunks[h] = nch;
+    hot.hot_u[h] = uid;
+    hot.hot_lo[h] = pv;
+    hot.hot_cnt[h] = c;
+    hot.hot_t0[h] = t0;
+  }
+  for (int cc = l; cc < nch; cc += stride) {
+    hot.task_u[t0 + cc] = uid;
+    hot.task_h[t0 + cc] = h;
+    hot.task_lo[t0 + cc] = pv + cc * hot.kchunk;
+    const int hi2 = pv + (cc + 1) * hot.kchunk;
+    hot.task_hi[t0 + cc] = hi2 < pv + c ? hi2 : pv + c;
+  }
+  if (nch > 1)
+    for (int e2 = l; e2 < hot.dim; e2 += stride) hot.hot_acc[(int64_t)h * hot.dim + e2] = 0.f;
+}
+
 template <int CAP, bool kW = false>   // kW: the records' weight sums (FusedArgs::rec_w) score the deferred inserts
 __global__ void __launch_bounds__(kP3Threads)
 fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restrict__ csr_src, HotList hot) {
@@ -1516,6 +1538,8 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
   __shared__ int s_nd, s_nbig;
   constexpr int kBigMax = 512;            // records with more than 8 occurrences (reference lists expanded wave by wave)
   __shared__ int b_pos[kBigMax], b_ref[kBigMax], b_cnt[kBigMax];
+  constexpr int kRegMax = 64;             // chunked hot rows a block registers wave by wave (more: by the row's own thread)
+  __shared__ int s_nreg, g_h[kRegMax], g_u[kRegMax], g_lo[kRegMax], g_cnt[kRegMax], g_t0[kRegMax];
   QST(0);
   constexpr int kDefMax = kPartCap / 4;
   const int p = blockIdx.x;
@@ -1531,7 +1555,7 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
   if (threadIdx.x < 256) s_lock[threadIdx.x] = 0;
   if (threadIdx.x < kP2Hash / 32) s_late[threadIdx.x] = 0;
   if (threadIdx.x < kPartCap / 4 / 32) s_fresh[threadIdx.x] = 0;
-  if (threadIdx.x == 0) { s_nd = 0; s_nbig = 0; }
+  if (threadIdx.x == 0) { s_nd = 0; s_nbig = 0; s_nreg = 0; }
   QST(1);
   __syncthreads();
   QST(2);
@@ -1686,21 +1710,11 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
         const int h = h_ex++, t0 = t_ex;
         t_ex += nch;
         if (h < hot.max_hot && t0 + nch <= hot.max_tasks) {
-          hot.hot_done[h] = 0;
-          hot.hot_nchunks[h] = nch;
-          hot.hot_u[h] = uid;
-          hot.hot_lo[h] = pv;
-          hot.hot_cnt[h] = c;
-          hot.hot_t0[h] = t0;
-          for (int cc = 0; cc < nch; ++cc) {
-            hot.task_u[t0 + cc] = uid;
-            hot.task_h[t0 + cc] = h;
-            hot.task_lo[t0 + cc] = pv + cc * hot.kchunk;
-            const int hi2 = pv + (cc + 1) * hot.kchunk;
-            hot.task_hi[t0 + cc] = hi2 < pv + c ? hi2 : pv + c;
-          }
-          if (nch > 1)
-            for (int e2 = 0; e2 < hot.dim; ++e2) hot.hot_acc[(int64_t)h * hot.dim + e2] = 0.f;
+          // the row's tasks and its zeroed accumulator are written by a whole wave behind the next barrier (a 20 K-occurrence
+          // row is 20 tasks of four words and `dim` floats: from this thread alone it held its block 2 us behind the others)
+          const int r = atomicAdd(&s_nreg, 1);
+          if (r < kRegMax) { g_h[r] = h; g_u[r] = uid; g_lo[r] = pv; g_cnt[r] = c; g_t0[r] = t0; }
+          else register_hot_row(hot, h, uid, pv, c, t0, 0, 1);
         }
       }
       ++uid; pv += c;
@@ -1726,12 +1740,19 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
       else for (int j = 0; j < cn; ++j) csr_src[pos + j] = ~(br + j);
     }
   }
+  QST(8);
   __syncthreads();
   {
+    const int nreg = s_nreg < kRegMax ? s_nreg : kRegMax;
+    for (int r = threadIdx.x >> 6; r < nreg; r += kP3Threads >> 6) register_hot_row(hot, g_h[r], g_u[r], g_lo[r], g_cnt[r], g_t0[r], lane_id(), 64);
+  }
+  {
+    // long lists by groups of 16 lanes, not by whole waves: a head key's list is 20..80 entries per tile, and what its owner pays
+    // is the LDS round trips of each list in turn (256 lists: 16 turns per wave, 4 per wave with four groups)
     const int nbig = s_nbig < kBigMax ? s_nbig : kBigMax;
-    for (int q = threadIdx.x >> 6; q < nbig; q += kP3Threads >> 6) {
+    for (int q = threadIdx.x >> 4; q < nbig; q += kP3Threads >> 4) {
       const int pos = b_pos[q], br = b_ref[q], cn = b_cnt[q];
-      for (int j = lane_id(); j < cn; j += 64) csr_src[pos + j] = ~(br + j);
+      for (int j = threadIdx.x & 15; j < cn; j += 16) csr_src[pos + j] = ~(br + j);
     }
   }
   // unique rows in front of the partition's table (the first partition of every table; partitions are table-major)
@@ -1750,7 +1771,6 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
     *o.total = O;
     if (U) ptr[U] = O;
   }
-  QST(8);
   QST(9);
 }
 

@@ -30,6 +30,8 @@ if a.batches <= 6:
             module._forward_impl(k, o, train=True)
 for k, o in batches:
     out, st = module._forward_impl(k, o, train=True)
+    nu = int(st.uoff[-1])      # (read before the backward hands the step's buffer back)
+    last = (k.cpu().numpy(), st.rev.cpu().numpy(), st.slots[:nu].cpu().numpy(), st.csr_cnt[:nu].cpu().numpy())
     module._backward_impl(st, grad)
 torch.cuda.synchronize()
 lib = ctypes.CDLL(mi355_native.LIB_PATH)
@@ -55,6 +57,7 @@ def dump(fn, nblk, nph, names, title, nlive=None):
     assert f(buf.ctypes.data, buf.nbytes) == 0
     live = buf[:, 0] != 0
     d = buf[live].astype(np.float64)
+    blk = np.nonzero(live)[0]
     if d.shape[0] == 0:
         print(f"{title}: no stamps recorded")
         return
@@ -70,7 +73,7 @@ def dump(fn, nblk, nph, names, title, nlive=None):
     w0, w1 = d[:, nph], d[:, nph + 1]
     ok = w1 > 0
     recent = w0 > w0.max() - 6000        # (blocks only an earlier launch used keep their old stamps: drop what is > 60 us older)
-    d, w0, w1, ok, life = d[recent], w0[recent], w1[recent], ok[recent], life[recent]
+    d, w0, w1, ok, life, blk = d[recent], w0[recent], w1[recent], ok[recent], life[recent], blk[recent]
     t0 = w0.min()
     SPANS.append((title.split(":")[0].split(" (")[0], w0.min() / 100.0, w1[ok].max() / 100.0))
     print(f"   wall clock (us, 100 MHz): starts {((w0 - t0) / 100).min():.2f} .. {((w0 - t0) / 100).max():.2f}  "
@@ -83,6 +86,53 @@ def dump(fn, nblk, nph, names, title, nlive=None):
         qs = [0, 10, 25, 50, 75, 90, 100]
         print("   start percentiles (us):", " ".join(f"{np.percentile(st, q):.1f}" for q in qs))
         print("   end   percentiles (us):", " ".join(f"{np.percentile(en, q):.1f}" for q in qs))
+    return blk[ok], (w1[ok] - t0) / 100, d[ok]
+
+
+def partition_load(keys, rev, slots, cnt):
+    """Per slot-range partition of the stamped step, rebuilt on the host from the step's own outputs (a partition is `spp`
+    consecutive slots; the probe kernel cuts the batch into contiguous tiles of `tl` keys and emits one record per (tile, key)):
+    (tile, key) records, CSR entries, records with more than 8 occurrences, unique rows, and the batch rank of its hottest key."""
+    tb = module.table
+    n, nu = len(keys), len(slots)
+    lib.mi355_demb_forward_fused_partitions.argtypes = [ctypes.c_longlong] * 3
+    P = lib.mi355_demb_forward_fused_partitions(n, 1, tb.num_buckets_)
+    C = tb.bucket_capacity_
+    spp = (-(-(tb.capacity_ + 1) // P) + C - 1) // C * C
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    tl = min(max((-(-n // ncu) + 63) // 64 * 64, 256), 2048 if n > ncu * 1024 else 1024)
+    part_u = (slots // spp).astype(np.int64)
+    assert (np.diff(part_u) >= 0).all(), "unique rows are not in partition order"
+    pair, pc = np.unique((np.arange(n) // tl) * nu + rev, return_counts=True)      # one record per (tile, unique row)
+    pp = part_u[pair % nu]
+    rec = np.bincount(pp, minlength=P)
+    ent = np.bincount(pp, weights=pc, minlength=P).astype(np.int64)
+    big = np.bincount(pp, weights=pc > 8, minlength=P).astype(np.int64)
+    uni = np.bincount(part_u, minlength=P)
+    assert (ent == np.bincount(part_u, weights=cnt, minlength=P)).all()
+    rank = np.empty(nu, np.int64)
+    rank[np.argsort(-cnt, kind="stable")] = np.arange(1, nu + 1)
+    top = np.full(P, nu + 1, np.int64)
+    np.minimum.at(top, part_u, rank)
+    return P, rec, ent, big, uni, top
+
+
+def tail_report(blk, end, d, names, load):
+    """the five partition blocks that end last, their load, and whether they are the owners of the batch's hottest keys"""
+    P, rec, ent, big, uni, top = load
+    print(f"   per partition: records mean {rec.mean():.0f} max {rec.max()}  entries mean {ent.mean():.0f} max {ent.max()}  "
+          f"long records (> 8) mean {big.mean():.1f} max {big.max()}  unique rows mean {uni.mean():.0f} max {uni.max()}")
+    last = np.argsort(-end)[:5]
+    for i in last:
+        p = blk[i]
+        ph = np.diff(d[i, :len(names) + 1])
+        j = int(np.argmax(ph / np.maximum(np.median(np.diff(d[:, :len(names) + 1], axis=1), axis=0), 1)))
+        print(f"   partition {p:4d} ends {end[i]:6.2f} us: {rec[p]:5d} records {ent[p]:6d} entries {big[p]:4d} long {uni[p]:4d} unique, "
+              f"hottest key rank {top[p]:5d}; phase furthest over its p50: '{names[j]}' {ph[j]:.0f} cyc")
+    owners = set(np.argsort(top)[:5].tolist())
+    print(f"   owners of the 5 hottest keys: {sorted(owners)}; of the 5 last-ending blocks {len(owners & set(blk[last].tolist()))} are among them; "
+          f"corr(end, entries) {np.corrcoef(end, ent[blk])[0, 1]:.2f}  corr(end, records) {np.corrcoef(end, rec[blk])[0, 1]:.2f}  "
+          f"corr(end, long records) {np.corrcoef(end, big[blk])[0, 1]:.2f}")
 
 
 PROBE_C = ['start -> loads issued + LDS init + barrier 0', 'hash + bucket + digest prefetch issue + bag marks', 'wait: barrier A', 'LDS dedup (+ pair histogram) + bag scan half 1', 'wait: barrier B', 'reservation issued, reps, list starts, 2 key words issued, bag scan half 2', 'wait: barrier C', 'list starts, probe resolve, scores, reserved bases', 'wait: barrier D', '-', 'records + per-occurrence outputs']
@@ -94,7 +144,7 @@ if os.environ.get("MI355_FUSED_PART", "2") == "1":
     dump("mi355_debug_stamps_part", 1024, 10, PART, "fused_part_kernel")
     dump("mi355_debug_stamps_scatter", 2048, 6, SCAT, "csr_scatter_kernel")
 PART2 = ["start -> record loads issued + LDS init", "wait: barrier", "merge (LDS hash insert + counts + rank bases out)", "wait: barrier",
-         "entry scan + publish sums", "look-back", "outputs per unique row", "outputs per record (CSR entries)", "-"]
+         "entry scan + publish sums", "look-back", "outputs per unique row", "outputs per record (CSR entries <= 8)", "wait: barrier + long lists, hot-row tasks"]
 PART_L = ["init + barrier", "merge pass", "wait: barrier", "eviction check, entry sums, block scan, publish", "look-back",
           "unique-row outputs (+ keys)", "wait: barrier", "output pass (CSR entries)", "tail", "-"]
 EVICT = ["entry -> bucket lock taken", "re-probe of the bucket", "score scan: the lane's minimum + its eligibility",
@@ -105,7 +155,9 @@ if os.environ.get("MI355_FUSED_PART", "2") != "1":
 if False:
     dump("mi355_debug_stamps_part", 1024, 10, PART_L[:9], "part3_lean (partition role of the gather's launch)")
 elif os.environ.get("MI355_FUSED_PART", "2") != "1":
-    dump("mi355_debug_stamps_part", 1024, 10, PART2, "fused_part3_kernel")
+    r = dump("mi355_debug_stamps_part", 1024, 10, PART2, "fused_part3_kernel")
+    if r is not None and len(r[0]) > 1:
+        tail_report(*r, PART2, partition_load(*last))
     dump("mi355_debug_stamps_fgather", 16384, 2, None, "gather_pooled_late_kernel (thread 0 of each block)")
 dump("mi355_debug_stamps_gather", 16384, 2, None, "gather_pooled_pipe_kernel (thread 0 of each block)")
 dump("mi355_debug_stamps_bwd", 16384, 2, None, "bwd_kernel (thread 0 of each block)")
