@@ -181,6 +181,29 @@ int mi355_expand_table_ids(const int64_t* offsets, int64_t num_tables, int64_t n
 int mi355_get_table_range(const int64_t* offsets, const int64_t* feature_offsets, int64_t num_tables,
                           int64_t feature_x_batch, int64_t* table_range, hipStream_t stream);
 
+/* INFERENCE_EMB::expand_table_ids, src/table_operation/expand_table_ids_torch_binding.cu:17-85: table_ids[i] = the largest
+ * t in [0, num_tables] with offsets[fo[t] * local_batch_size] <= i, fo = table_offsets_in_feature (int64[num_tables+1]) or the
+ * identity when it is NULL; then num_tables = (offsets_numel - 1) / local_batch_size, as the reference derives it. */
+int mi355_inference_expand_table_ids(const int64_t* offsets, int64_t offsets_numel, const int64_t* table_offsets_in_feature,
+                                     int64_t num_tables, int64_t local_batch_size, int64_t n, int64_t* table_ids,
+                                     hipStream_t stream);
+
+/* InferenceEmbeddingCollection.forward, dynamicemb/exportable_tables.py:501-564 (expand_table_ids + table_lookup under
+ * ScorePolicy.CONST + index_select / add + NVEmbedding / NVEmbeddingBag) as ONE read-only launch without a host sync.
+ * keys: 8-byte words [n]; offsets [offsets_numel]: CSR offsets of the feature slots; feature_offsets int64[num_tables+1] (NULL:
+ * identity); table arena: single-score LinearBucketTable storage (17 bytes per slot) with its table_bucket_offsets, read when
+ * use_dynamic_hash != 0 (bucket_capacity a power of two); otherwise a key is its own table-relative index.
+ * weight [rows, dim] of weight_dtype (0 fp32, 2 fp16): table t owns rows table_offsets[t] - 1 (its all-zero row, where unknown
+ * keys, out-of-range identity keys and out-of-range slots land) .. table_offsets[t + 1] - 2.
+ * pooling_mode -1: out [n, dim], a copy of the rows.  1 / 2: out [num_bags, dim] = sum / mean over pooling_offsets
+ * (int64[num_bags+1]) with fp32 accumulation in key order, optional per_sample_weights fp32[n] (sum only); out has weight_dtype. */
+int mi355_inference_emb_forward(const void* keys, int64_t n, const int64_t* offsets, int64_t offsets_numel,
+                                const int64_t* feature_offsets, int64_t num_tables, int64_t local_batch_size,
+                                const void* table_storage, const int64_t* table_bucket_offsets, int64_t bucket_capacity,
+                                const int64_t* table_offsets, const void* weight, int64_t dim, int weight_dtype,
+                                const int64_t* pooling_offsets, int64_t num_bags, const float* per_sample_weights,
+                                int pooling_mode, int use_dynamic_hash, void* out, hipStream_t stream);
+
 /* flagged_compact, src/index_calculation.cu:129-232 -- order preserving; the count stays on the
  * device in *count_out (the reference syncs the host here).  Arrays are 8-byte words. */
 int64_t mi355_flagged_compact_workspace_bytes(int64_t n);

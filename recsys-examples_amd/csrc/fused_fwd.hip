@@ -1796,39 +1796,7 @@ __global__ void __launch_bounds__(256) gather_pooled_late_kernel(PoolArgs g, Lat
 #endif
 }
 
-// A wave copies the 64 rows whose addresses its lanes hold (lane l: row i0 + l; 0 = no row -> zeros): 64 / LPR rows per step,
-// the addresses handed round with shuffles, UN steps' loads issued before their stores -- a wave keeps UN x 64 / LPR rows in flight
-// (one row per lane group and step left the copy latency bound: 2 K waves x 2 rows x 512 B = 2 MB in flight against the ~12 MB
-// that 8 TB/s x 1.5 us asks for).  Rows of one column group (D <= 4 LPR), 16-byte aligned; every load is unconditional (lanes
-// without a row read the zero row, see gather_dev.h).
-template <int SDT, int DDT>
-__device__ __forceinline__ void wave_copy_rows(uintptr_t rp, int64_t i0, int64_t n, int D, void* dst, int64_t dst_stride, int lpr_log2) {
-  constexpr int UN = 8;
-  constexpr int EB = SDT == kF32 ? 4 : 2;
-  const gptr_t zero = (gptr_t)(uintptr_t)g_zero_row;
-  const int lane = lane_id();
-  const int LPR = 1 << lpr_log2, R = 64 >> lpr_log2;
-  const int sub = lane >> lpr_log2, c = lane & (LPR - 1);
-  const int rlo = (int)(rp & 0xffffffffu), rhi = (int)(rp >> 32);
-  const bool col = 4 * c < D;
-  for (int q0 = 0; q0 < 64; q0 += R * UN) {
-    float4 v[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int src = (q0 + u * R + sub) & 63;
-      const uintptr_t ad = (uintptr_t)(unsigned)__shfl(rlo, src, 64) | ((uintptr_t)(unsigned)__shfl(rhi, src, 64) << 32);
-      const gptr_t p = (ad != 0 && col) ? (gptr_t)(ad + (uintptr_t)(4 * c * EB)) : zero;
-      v[u] = ld4g<SDT>(p);
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int src = q0 + u * R + sub;
-      const int64_t i = i0 + src;
-      if (src < 64 && i < n && col) st4<DDT>(dst, i * dst_stride + 4 * c, v[u]);
-    }
-  }
-}
-
+// (wave_copy_rows, the row copy of the sequence gathers below, lives in gather_dev.h)
 // sequence gather of path (c): out[j, :D] = the row of occurrence j, late rows through the key's record.  A wave owns 64
 // consecutive occurrences: one coalesced load of their address words, then wave_copy_rows.
 template <int SDT, int DDT>

@@ -65,6 +65,39 @@ __device__ __forceinline__ float4 ld4g(gptr_t p) {
   }
 }
 
+// A wave copies the 64 rows whose addresses its lanes hold (lane l: row i0 + l; 0 = no row -> zeros): 64 / LPR rows per step,
+// the addresses handed round with shuffles, UN steps' loads issued before their stores -- a wave keeps UN x 64 / LPR rows in flight
+// (one row per lane group and step left the copy latency bound: 2 K waves x 2 rows x 512 B = 2 MB in flight against the ~12 MB
+// that 8 TB/s x 1.5 us asks for).  Rows of one column group (D <= 4 LPR), 16-byte aligned; every load is unconditional (lanes
+// without a row read the zero row, see gather_dev.h).
+template <int SDT, int DDT>
+__device__ __forceinline__ void wave_copy_rows(uintptr_t rp, int64_t i0, int64_t n, int D, void* dst, int64_t dst_stride, int lpr_log2) {
+  constexpr int UN = 8;
+  constexpr int EB = SDT == kF32 ? 4 : 2;
+  const gptr_t zero = (gptr_t)(uintptr_t)g_zero_row;
+  const int lane = lane_id();
+  const int LPR = 1 << lpr_log2, R = 64 >> lpr_log2;
+  const int sub = lane >> lpr_log2, c = lane & (LPR - 1);
+  const int rlo = (int)(rp & 0xffffffffu), rhi = (int)(rp >> 32);
+  const bool col = 4 * c < D;
+  for (int q0 = 0; q0 < 64; q0 += R * UN) {
+    float4 v[UN];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int src = (q0 + u * R + sub) & 63;
+      const uintptr_t ad = (uintptr_t)(unsigned)__shfl(rlo, src, 64) | ((uintptr_t)(unsigned)__shfl(rhi, src, 64) << 32);
+      const gptr_t p = (ad != 0 && col) ? (gptr_t)(ad + (uintptr_t)(4 * c * EB)) : zero;
+      v[u] = ld4g<SDT>(p);
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int src = q0 + u * R + sub;
+      const int64_t i = i0 + src;
+      if (src < 64 && i < n && col) st4<DDT>(dst, i * dst_stride + 4 * c, v[u]);
+    }
+  }
+}
+
 // Late rows of the fused forward (fused_fwd.hip): a key whose bucket had no free slot gets its slot from the eviction kernel,
 // after the probe kernel wrote the per-occurrence addresses.  Such an occurrence carries the address word 1 and finds its row
 // through its (tile, key) record: occ_slot[j] = record, whose third word is the slot by then (>= S: no row this step).
@@ -269,14 +302,18 @@ struct EvalTab {
   int64_t bkt0, tp0, rowb;
   uint64_t nb, magic;
 };
-__device__ __forceinline__ EvalTab eval_tab_of(const EvalTabs& L, int T, int64_t j) {
-  int lo = 0, hi = T;      // first t with seg[t + 1] > j
+// table of the key at position j: the first t with seg[t + 1] > j
+__device__ __forceinline__ int eval_tab_index(const EvalTabs& L, int T, int64_t j) {
+  int lo = 0, hi = T;
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (L.seg[mid + 1] <= j) lo = mid + 1; else hi = mid; }
-  const int t = lo < T ? lo : T - 1;
+  return lo < T ? lo : T - 1;
+}
+__device__ __forceinline__ EvalTab eval_tab_at(const EvalTabs& L, int t) {
   EvalTab e;
   e.bkt0 = L.tbo[t]; e.nb = (uint64_t)(L.tbo[t + 1] - e.bkt0); e.magic = L.magic[t]; e.tp0 = L.tptr[t]; e.rowb = L.rowb[t];
   return e;
 }
+__device__ __forceinline__ EvalTab eval_tab_of(const EvalTabs& L, int T, int64_t j) { return eval_tab_at(L, eval_tab_index(L, T, j)); }
 
 // Row address of `key` in table `e` (0: unknown key / !have): digest vector, key word, row -- three dependent hops; a found key's
 // score is refreshed (score.cuh:72-96; idempotent across the key's occurrences).
@@ -324,8 +361,12 @@ __device__ __forceinline__ uintptr_t eval_probe_key(const ProbeRefs& pr, const E
 // addresses out of the lanes with shuffles.  Keys beyond the first LPR of the run (a few per cent of the groups at C2) are
 // probed when their bag is reached (dependent hops).
 // kMT: several tables -- `tabs` (LDS, eval_tabs_load) holds their scalars, a key's table follows from its position.
-template <int SDT, int DDT, int UNR, int KIT, bool kMT = false>
-__device__ __forceinline__ void gather_pooled_eval(const PoolArgs& a, ProbeRefs pr, int lpr_log2, int64_t sg, const EvalTabs* tabs = nullptr) {
+// Hook (inference_emb.hip): kRow -- the caller resolves a key to its row address itself, row(position, key, have); kWeights --
+// row i enters its bag as weight(position) * row, still one fused multiply-add per element in key order.
+struct NoEvalHook { static constexpr bool kRow = false, kWeights = false; };
+template <int SDT, int DDT, int UNR, int KIT, bool kMT = false, class Hook = NoEvalHook>
+__device__ __forceinline__ void gather_pooled_eval(const PoolArgs& a, ProbeRefs pr, int lpr_log2, int64_t sg, const EvalTabs* tabs = nullptr,
+                                                   const Hook& hook = Hook{}) {
   const int lane = lane_id();
   const int LPR = 1 << lpr_log2;
   const int c = lane & (LPR - 1);
@@ -361,11 +402,23 @@ __device__ __forceinline__ void gather_pooled_eval(const PoolArgs& a, ProbeRefs 
     jc = jc < 0 ? 0 : jc;
     jc = jc < a.n ? jc : a.n - 1;
     const uint64_t key = pr.keys[jc];
-    if constexpr (kMT) return eval_probe_key(pr, eval_tab_of(*tabs, pr.T, jc), key, have, C, cshift);
+    if constexpr (Hook::kRow) return hook.row(jc, key, have);
+    else if constexpr (kMT) return eval_probe_key(pr, eval_tab_of(*tabs, pr.T, jc), key, have, C, cshift);
     else return eval_probe_key(pr, one, key, have, C, cshift);
   };
-  // rows whose addresses sit in lanes base .. base + nq - 1 of `rp`
-  auto add_rows = [&](uintptr_t rp, int base, int nq, int Df, float4& acc) {
+  // weight of the key at position j (Hook::kWeights)
+  auto weigh = [&](int64_t j, int64_t jend) -> float {
+    if constexpr (Hook::kWeights) {
+      int64_t jc = j < jend ? j : jend - 1;
+      jc = jc < 0 ? 0 : jc;
+      jc = jc < a.n ? jc : a.n - 1;
+      return hook.weight(jc);
+    } else {
+      return 1.f;
+    }
+  };
+  // rows whose addresses sit in lanes base .. base + nq - 1 of `rp` (their weights in the same lanes of `wv`)
+  auto add_rows = [&](uintptr_t rp, float wv, int base, int nq, int Df, float4& acc) {
     const int rlo = (int)(rp & 0xffffffffu), rhi = (int)(rp >> 32);
     for (int q0 = 0; q0 < LPR; q0 += UNR) {
       if (__ballot(q0 < nq) == 0) break;
@@ -380,13 +433,22 @@ __device__ __forceinline__ void gather_pooled_eval(const PoolArgs& a, ProbeRefs 
         v[q] = ld4g<SDT>(p);
       }
 #pragma unroll
-      for (int q = 0; q < UNR; ++q) add4(acc, v[q]);
+      for (int q = 0; q < UNR; ++q) {
+        if constexpr (Hook::kWeights) {
+          float w = __shfl(wv, (base + q0 + q) & (LPR - 1), LPR);
+          w = q0 + q < nq ? w : 0.f;
+          acc.x = fmaf(w, v[q].x, acc.x); acc.y = fmaf(w, v[q].y, acc.y); acc.z = fmaf(w, v[q].z, acc.z); acc.w = fmaf(w, v[q].w, acc.w);
+        } else {
+          add4(acc, v[q]);
+        }
+      }
     }
   };
   const int64_t run_lo = bag_off(0);
   int64_t run_hi = bag_off(KIT);
   run_hi = run_hi < a.n ? run_hi : a.n;
   const uintptr_t rp0 = probe(run_lo + c, run_hi);      // the run's first LPR keys, one per lane
+  const float w0 = weigh(run_lo + c, run_hi);
 #pragma unroll
   for (int it = 0; it < KIT; ++it) {
     const int64_t bag = bag0 + it;
@@ -402,13 +464,14 @@ __device__ __forceinline__ void gather_pooled_eval(const PoolArgs& a, ProbeRefs 
     const int64_t in_first = run_lo + LPR - lo_c;      // keys of the bag covered by rp0 (may be <= 0 or >= L)
     if (__ballot(in_first > 0 && L > 0)) {
       const int64_t nq = in_first < L ? (in_first > 0 ? in_first : 0) : L;
-      add_rows(rp0, (int)(lo_c - run_lo), (int)nq, Df, acc);
+      add_rows(rp0, w0, (int)(lo_c - run_lo), (int)nq, Df, acc);
       r = nq;
     }
     for (; __ballot(r < L) != 0; r += LPR) {
       const uintptr_t rr = probe(lo_c + r + c, hi_c);
+      const float wr = weigh(lo_c + r + c, hi_c);
       const int64_t left = L - r;
-      add_rows(rr, 0, (int)(left < 0 ? 0 : (left < LPR ? left : LPR)), Df, acc);
+      add_rows(rr, wr, 0, (int)(left < 0 ? 0 : (left < LPR ? left : LPR)), Df, acc);
     }
     if (a.combiner == 1 && L > 0) {
       const float fl = (float)L;

@@ -1832,12 +1832,10 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
 
     def load(self, save_dir: str, optim: bool = False, counter: bool = False, table_names: Optional[List[str]] = None,
              pg=None) -> None:
-        import glob
         import json
         import os
 
-        import numpy as np
-
+        from .dump_load import dump_key_files, iter_dump_batches
         from .scored_hashtable import ScoreArg
 
         rank, world = self._rank_world(pg)
@@ -1847,7 +1845,7 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
         for t, name in enumerate(self._table_names):
             if name not in set(names):
                 continue
-            key_files = sorted(glob.glob(os.path.join(save_dir, f"{name}_emb_keys.rank_*.world_size_*")))
+            key_files = dump_key_files(save_dir, name)
             if not key_files:
                 continue
             meta_path = os.path.join(save_dir, f"{name}_opt_args.json")
@@ -1865,43 +1863,27 @@ class BatchedDynamicEmbeddingTablesV2(nn.Module):
             D, V = self.dims[t], self.value_dims[t]
             cs = self._ckpt_state_dim(D)
             for kf in key_files:
-                suffix = kf[kf.index("_emb_keys") + len("_emb_keys"):]
-                path = lambda item: os.path.join(save_dir, f"{name}_emb_{item}{suffix}")  # noqa: E731
-                nkeys = os.path.getsize(kf) // 8
-                B = 1 << 16
-                with open(kf, "rb") as fk, open(path("values"), "rb") as fv:
-                    fs = open(path("scores"), "rb") if os.path.exists(path("scores")) else None
-                    fo = open(path("opt_values"), "rb") if (use_opt and cs and os.path.exists(path("opt_values"))) else None
-                    for start in range(0, nkeys, B):
-                        n = min(B, nkeys - start)
-                        keys = np.frombuffer(fk.read(8 * n), dtype=np.int64)
-                        emb = np.frombuffer(fv.read(4 * D * n), dtype=np.float32).reshape(n, D)
-                        sc = np.frombuffer(fs.read(8 * n), dtype=np.int64) if fs else None
-                        op = np.frombuffer(fo.read(4 * cs * n), dtype=np.float32).reshape(n, cs) if fo else None
-                        if world > 1:
-                            m = (keys % world) == rank
-                            keys, emb = keys[m], emb[m]
-                            sc = sc[m] if sc is not None else None
-                            op = op[m] if op is not None else None
-                        if keys.size == 0:
-                            continue
-                        k_t = torch.from_numpy(keys.copy()).to(dev)
-                        rows = torch.full((keys.size, V), float(self.initial_accumulator_value), dtype=torch.float32, device=dev)
-                        rows[:, :D] = torch.from_numpy(emb.copy()).to(dev)
-                        if op is not None:
-                            rows[:, D:D + cs] = torch.from_numpy(op.copy()).to(dev)
-                        elif self._opt_kind == 2:
-                            rows[:, D:] = 0.0
-                        if sc is not None:
-                            s_t = torch.from_numpy(sc.copy()).to(dev)
-                            s_t = (now - s_t) if self._is_lru() else s_t
-                        else:
-                            s_t = torch.full((keys.size,), now if self._is_lru() else 0, dtype=torch.int64, device=dev)
-                        self._insert_rows(t, k_t, rows.to(self.embedding_dtype), s_t)
-                    if fs:
-                        fs.close()
-                    if fo:
-                        fo.close()
+                for keys, emb, sc, op in iter_dump_batches(save_dir, name, kf, D, cs if use_opt else 0):
+                    if world > 1:
+                        m = (keys % world) == rank
+                        keys, emb = keys[m], emb[m]
+                        sc = sc[m] if sc is not None else None
+                        op = op[m] if op is not None else None
+                    if keys.size == 0:
+                        continue
+                    k_t = torch.from_numpy(keys.copy()).to(dev)
+                    rows = torch.full((keys.size, V), float(self.initial_accumulator_value), dtype=torch.float32, device=dev)
+                    rows[:, :D] = torch.from_numpy(emb.copy()).to(dev)
+                    if op is not None:
+                        rows[:, D:D + cs] = torch.from_numpy(op.copy()).to(dev)
+                    elif self._opt_kind == 2:
+                        rows[:, D:] = 0.0
+                    if sc is not None:
+                        s_t = torch.from_numpy(sc.copy()).to(dev)
+                        s_t = (now - s_t) if self._is_lru() else s_t
+                    else:
+                        s_t = torch.full((keys.size,), now if self._is_lru() else 0, dtype=torch.int64, device=dev)
+                    self._insert_rows(t, k_t, rows.to(self.embedding_dtype), s_t)
 
     def flush(self) -> None:
         """write-back of a promoting cache (batched_dynamicemb_tables.py:955); the tiers here hold each key once"""

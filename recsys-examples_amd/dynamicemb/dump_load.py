@@ -2,11 +2,43 @@
 model in the reference's wire format -- one folder per embedding collection (named by the collection's path in the model),
 per table and rank the raw little-endian files `<table>_emb_{keys,values,scores,opt_values}.rank_R.world_size_W` plus
 `<table>_opt_args.json` (written / read by BatchedDynamicEmbeddingTablesV2.dump / .load)."""
+import glob
 import os
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch.distributed as dist
 from torch import nn
+
+
+def dump_key_files(save_dir: str, table_name: str) -> List[str]:
+    """the key files of one table in a dump folder, every rank's"""
+    return sorted(glob.glob(os.path.join(save_dir, f"{table_name}_emb_keys.rank_*.world_size_*")))
+
+
+def iter_dump_batches(save_dir: str, table_name: str, key_file: str, dim: int, opt_dim: int = 0, batch: int = 1 << 16):
+    """Batches of one rank's files of a table (`key_file` is one of `dump_key_files`): NumPy arrays
+    (keys i64[n], embeddings f32[n, dim], scores i64[n] or None, optimizer state f32[n, opt_dim] or None).  Scores are None when
+    the score file is missing; the optimizer state when opt_dim == 0 or its file is missing."""
+    suffix = key_file[key_file.index("_emb_keys") + len("_emb_keys"):]
+    path = lambda item: os.path.join(save_dir, f"{table_name}_emb_{item}{suffix}")  # noqa: E731
+    nkeys = os.path.getsize(key_file) // 8
+    with open(key_file, "rb") as fk, open(path("values"), "rb") as fv:
+        fs = open(path("scores"), "rb") if os.path.exists(path("scores")) else None
+        fo = open(path("opt_values"), "rb") if (opt_dim and os.path.exists(path("opt_values"))) else None
+        try:
+            for start in range(0, nkeys, batch):
+                n = min(batch, nkeys - start)
+                keys = np.frombuffer(fk.read(8 * n), dtype=np.int64)
+                emb = np.frombuffer(fv.read(4 * dim * n), dtype=np.float32).reshape(n, dim)
+                sc = np.frombuffer(fs.read(8 * n), dtype=np.int64) if fs else None
+                op = np.frombuffer(fo.read(4 * opt_dim * n), dtype=np.float32).reshape(n, opt_dim) if fo else None
+                yield keys, emb, sc, op
+        finally:
+            if fs:
+                fs.close()
+            if fo:
+                fo.close()
 
 
 def _unwrap(m: nn.Module) -> nn.Module:

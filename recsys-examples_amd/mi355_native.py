@@ -60,6 +60,12 @@ _SIGS = {
     "mi355_group_by_unique_csr_workspace_bytes": [c_i64],
     "mi355_expand_table_ids": [c_p, c_i64, c_i64, c_p, c_p, c_p],
     "mi355_get_table_range": [c_p, c_p, c_i64, c_i64, c_p, c_p],
+    "mi355_inference_expand_table_ids": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p],
+    "mi355_inference_emb_forward": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64,  # keys, feature slots, tables
+                                    c_p, c_p, c_i64,  # table arena
+                                    c_p, c_p, c_i64, c_int,  # weight
+                                    c_p, c_i64, c_p, c_int, c_int,  # pooling, mode, hash
+                                    c_p, c_p],
     "mi355_flagged_compact": [c_p, c_i64, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_i64, c_p],
     "mi355_group_by_unique": [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p],
     "mi355_hot_rows_workspace_bytes": [c_i64, c_i64],
