@@ -629,7 +629,7 @@ def test_mask_functions_on_the_exchange_backward_match_the_recomputing_passes_bi
 
 @pytest.mark.parametrize("rule", ["causal", "window"])
 def test_a_built_in_mask_written_as_functions_is_bit_identical_to_the_built_in_kernels(rule):
-    """A size-independent property at 4 x 2048 (the oracle takes minutes there): the causal mask written as a prefix function
+    """A size-independent property at 4 x 2048 (the oracle comparison at this length is tests/test_hstu_long_gpu.py): the causal mask written as a prefix function
     (key j < i + 1) and a local window written as one band (i - wl <= j < i + wr + 1) give the outputs and gradients of the causal /
     window kernels bit for bit -- same tiles, same MFMA order, the masked elements exact zeros either way (d = 256: two-wave-kind
     forward, exchange backward on both sides; the function side in the dense exchange layout, the causal side in the triangular one)."""
@@ -710,7 +710,7 @@ def test_mask_functions_allocate_no_mask_tensor():
                                     func=func)
     torch.cuda.synchronize()
     assert torch.cuda.max_memory_allocated() - base < 2 * q.numel() * q.element_size()
-    sel = np.r_[0:40, 4000:4096, 4096:4130, 8100:8192]          # a few hundred rows against the oracle (the whole batch takes minutes)
+    sel = np.r_[0:40, 4000:4096, 4096:4130, 8100:8192]          # a few hundred rows against the oracle (whole long batches: tests/test_hstu_long_gpu.py)
     qn, kn, vn = (t.float().cpu().numpy() for t in (q, k, v))
     ref = ho.hstu_attn_fwd(qn, kn, vn, off, 0.125, 4096, causal=False, func=f)
     err = np.abs(out.float().cpu().numpy()[sel] - ref[sel]).max()
