@@ -916,6 +916,37 @@ int mi355_hstu_attn_bwd_fp8(int quant_mode, const void* dout, const void* dout_t
                             const int32_t* cu_seqlens_block_descale_q, const int32_t* cu_seqlens_block_descale_kv,
                             hipStream_t stream);
 
+/* ---- hstu_cuda_ops: jagged row movers between the embedding output and the attention input (csrc/jagged_ops.hip) ----
+ * Reference paths below are relative to the reference's examples/commons/ops/cuda_ops/.  dtype codes as everywhere
+ * (0 fp32, 1 bf16, 2 fp16) plus 3 = fp64 for these entry points: rows are moved as bytes. */
+
+/* Concat of n (1..128) jagged 2-D tensors with one hidden dim D and one batch, and its inverse: replaces
+ * concat_2D_jagged_tensors_cuda_forward / _backward (csrc/jagged_tensor_op_kernel.cu; op schema
+ * csrc/jagged_tensor_op_cuda.cpp:243-244).  values / offsets / rows are HOST arrays of n entries (device pointer of tensor t,
+ * device pointer of its int64 offsets [batch + 1], its row count); they travel to the kernel as arguments, nothing is staged.
+ * direction 0: merged[merged_offsets[b] + sum_{t' < t} len_t'[b] + r, :] = values_t[offsets_t[b] + r, :];
+ * direction 1: the inverse, every row of every values_t is written.  merged: [total_rows, D].  One launch, no host sync, no
+ * allocation; a row index outside its tensor (inconsistent offsets) is skipped, never accessed. */
+int mi355_jagged_concat(int n, const void* const* values, const int64_t* const* offsets, const int64_t* rows, int64_t batch,
+                        const int64_t* merged_offsets, void* merged, int64_t total_rows, int64_t D, int dtype,
+                        int direction, hipStream_t stream);
+
+/* compute_block_workloads (csrc/jagged_tensor_op_kernel.cu; schema csrc/jagged_tensor_op_cuda.cpp:245): with
+ * nb = ceil(max_seqlen / seqlen_per_block), workloads[(b n + t) nb + idx] = max(0, min(len_t[b] - idx seqlen_per_block,
+ * seqlen_per_block)).  offsets: HOST array of n device pointers.  Only the reference's Python wrapper needs it. */
+int mi355_jagged_block_workloads(int n, const int64_t* const* offsets, int64_t batch, int64_t seqlen_per_block,
+                                 int64_t max_seqlen, int64_t* workloads, int64_t workloads_numel, hipStream_t stream);
+
+/* Row movement of hstu_inference_preprocess (csrc/jagged_tensor_op_cuda.cpp:135-240, a host loop of narrow().copy_() there) in
+ * one launch.  Per sample with I items, A actions (e = A - I in {0, 1}) and C candidates, h = I - C: output row r is
+ * action[0] if r < e; with r' = r - e: item[r' / 2] (r' < 2 h, even), action[r' / 2 + e] (r' < 2 h, odd), else
+ * item[h + r' - 2 h]; the candidates' action rows are dropped.  All offsets are device int64 [batch + 1]; C follows from
+ * them (out length = 2 h + e + C). */
+int mi355_hstu_inference_preprocess(const void* item_values, int64_t item_rows, const int64_t* item_offsets,
+                                    const void* action_values, int64_t action_rows, const int64_t* action_offsets,
+                                    const int64_t* out_offsets, int64_t batch, void* out, int64_t out_rows, int64_t D,
+                                    int dtype, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

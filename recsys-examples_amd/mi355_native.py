@@ -187,6 +187,9 @@ _SIGS = {
     "mi355_hstu_attn_bwd_fp8": [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64,
                                 c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_p],
+    "mi355_jagged_concat": [c_int, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p],
+    "mi355_jagged_block_workloads": [c_int, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p],
+    "mi355_hstu_inference_preprocess": [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
