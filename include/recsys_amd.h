@@ -772,6 +772,27 @@ int mi355_hstu_attn_bwd_rab(const void* dout, const void* q, const void* k, cons
                             int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
                             int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
                             int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream);
+/* Delta-q backward: gradients of mi355_hstu_attn_fwd_kv / _kv_window / _kv_rab without a paged cache (hstu_bwd.h:98:
+ * actual_seqlen_offset = actual_seqlen_k - actual_seqlen_q shifts every tile bound and mask of the reference's backward, :102-123,
+ * 191-198,565-616; its kernel tests differentiate such calls, corelib/hstu/test.py:667-720).  The queries of sequence b (rows
+ * cu_seqlens_q[b] .. of q / dout / dq) are the LAST Lq of its Lk keys (rows cu_seqlens_k[b] .. of k / v / dk / dv): query r sits
+ * at the absolute position Lk - Lq + r, where the masks and rab[b][h][Lk - Lq + r][j] are taken.  Mask as window_size: (-1, 0)
+ * causal (num_contexts / num_targets allowed), (-1, -1) full, otherwise a local window.  rab (nullable) as for
+ * mi355_hstu_attn_fwd_kv_rab; drab (nullable, needs rab): one [max_seqlen_k][max_seqlen_k] matrix per head, zero-filled by the
+ * caller -- rows in front of a sequence's first query and everything outside the sequence stay zero.  dq contiguous
+ * [total_q, H, d], dk / dv contiguous [total_k, H, d]; every row is written (a sequence without queries, keys no query reaches:
+ * zeros).  Deterministic, no scratch: the recomputing passes, their query / key tile loops clipped to what the shifted mask
+ * reaches.  max_seqlen_q > max_seqlen_k is refused (MI355_EINVAL); Lq > Lk in a single sequence is visible on the device only
+ * and undefined, as in the forward -- the passes then touch nothing of that sequence and its gradient rows stay unwritten. */
+int mi355_hstu_attn_bwd_kv(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                           int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                           int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                           const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads,
+                           int64_t head_dim, int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                           const int32_t* num_targets, int64_t target_group_size, int64_t window_left, int64_t window_right,
+                           float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride,
+                           int64_t rab_head_stride, int64_t rab_row_stride, void* drab, int64_t drab_batch_stride,
+                           int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream);
 /* Optional scratch of mi355_hstu_attn_bwd: given a 16-byte aligned workspace of at least this many bytes, the dK pass
  * hands dS to the dQ pass through it (bf16, B * H * ceil(max_seqlen/32)^2 sub-tiles of 2 KB) and the dQ pass skips the
  * S / dP recomputation (head_dim >= 128: P travels too and the dV pass becomes one GEMM); with a smaller (or no)
@@ -854,6 +875,15 @@ int mi355_hstu_attn_bwd_rab_f16(const void* dout, const void* q, const void* k, 
                             int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
                             int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
                             int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream);
+int mi355_hstu_attn_bwd_kv_f16(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                           int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                           int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                           const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads,
+                           int64_t head_dim, int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                           const int32_t* num_targets, int64_t target_group_size, int64_t window_left, int64_t window_right,
+                           float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride,
+                           int64_t rab_head_stride, int64_t rab_row_stride, void* drab, int64_t drab_batch_stride,
+                           int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream);
 
 
 /* ---- HSTU attention on FP8 (OCP e4m3fn) operands (csrc/hstu_fp8.hip) ----

@@ -2110,12 +2110,58 @@ __device__ __forceinline__ int2 func_kvis_of(const BwdAttnArgs& g, int start, in
   return make_int2(0, 0x7fffffff);
 }
 
+// ---- delta-q backward (hstu_bwd.h:98: actual_seqlen_offset = actual_seqlen_k - actual_seqlen_q carried through every bound).
+// The queries of sequence b are rows cu_seqlens[b] .. of q / dout / dq and sit at the absolute positions qoff + r, qoff = Lk - Lq,
+// of its Lk keys (cu_seqlens_k); every mask is the self-attention mask of a sequence of Lk tokens.  The passes below take it as
+// the template flag kDq: their step loops run over ROWS of q (so the staging needs no negative rows) and add qoff wherever a
+// position meets a mask, the bias or a tile bound.  Without the flag qstart / Lq / qoff are the sequence's own start, length and 0.
+struct QRows { int qstart, Lq, qoff; };
+template <bool kDq>
+__device__ __forceinline__ BlockSeq key_seq_of_block(const AttnArgs& a) {
+  if constexpr (kDq) {   // plain grid (H, B, blocks): the rotated / column-major maps are built on ONE offset array
+    const int b = blockIdx.y;
+    return BlockSeq{b, (int)blockIdx.x, a.cu_seqlens_k[b], a.cu_seqlens_k[b + 1], (int)blockIdx.z};
+  } else {
+    return seq_head_of_block(a);
+  }
+}
+template <bool kDq>
+__device__ __forceinline__ QRows q_rows_of(const AttnArgs& a, int b, const SeqInfo& s) {
+  if constexpr (kDq) {
+    const int q0 = a.cu_seqlens[b], lq = a.cu_seqlens[b + 1] - q0;
+    return QRows{q0, lq, s.L - lq};
+  } else {
+    return QRows{s.start, s.L, 0};
+  }
+}
+// kv_span in rows of q for the delta-q dK / dV pass: the steps [0, c_end) and [jump, lim) of `bq` rows whose absolute positions
+// qoff + r can see the key block n0 .. n0 + kBM - 1.  Causal: from the row at position n0 on, plus the contextual rows that are
+// queries (positions < c); window: rows n0 - wr .. n0 + kBM - 1 + wl; a block of target keys only: up to the end of the group of
+// its last key (hstu_bwd.h:102-127).  An empty range (Lq = 0, keys right of every window) leaves the block's dK / dV rows zero.
+__device__ __forceinline__ KvSpan kv_span_dq(const AttnArgs& a, const SeqInfo& s, int n0, int bq, const QRows& qr) {
+  KvSpan v{0, 0, qr.Lq};
+  const auto step_of = [&](int pos) { const int r = pos - qr.qoff; return r > 0 ? (r / bq) * bq : 0; };
+  const auto clip_lim = [&](int pos_end) { const int r = pos_end - qr.qoff; if (r < v.lim) v.lim = r > 0 ? r : 0; };
+  if (a.causal) {
+    v.jump = step_of(n0);
+    if (s.has_ctx && s.c > qr.qoff && n0 < s.hlen) v.c_end = ((s.c - qr.qoff + bq - 1) / bq) * bq;
+    if (s.has_tgt && n0 >= s.hlen) {
+      const int last_key = n0 + kBM - 1 < s.L - 1 ? n0 + kBM - 1 : s.L - 1;
+      clip_lim(s.hlen + ((last_key - s.hlen) / a.group + 1) * a.group);
+    }
+  } else if (a.wskip && a.wr >= 0 && n0 > a.wr) {
+    v.jump = step_of(n0 - a.wr);
+  }
+  if (a.wskip && a.wl >= 0) clip_lim(n0 + kBM + a.wl);
+  return v;
+}
+
 // pass A: one workgroup = 128 keys (32 per wave) of one (sequence, head); loops over query tiles of BQ rows.
 // MODE 0: dV and dK together (d <= 64).  Larger d: the two output accumulators plus the S / dP accumulators and the
 // K / V fragments exceed the register file of one wave, so the pass is split: MODE 1 = dV only (S -> P -> dV),
 // MODE 2 = dK only (S, dP -> dS -> dK).  Loop structure as in the forward: register-prefetched tiles, explicit
 // AGPR output accumulators, double-buffered LDS fragment batches, branch-free mask.
-template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false>
+template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
 __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;   // kXP (MODE 2): P is computed as well and left for the dV pass
@@ -2128,7 +2174,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   uint16_t* Qt = dOs + (kDK ? BQ * RS : 0);         // [BQ][TRS]  (dK; kDK only)
   uint16_t* dOt = Qt + (kDK ? TIMG : 0);            // [BQ][TRS]  (dV; kDV only)
 
-  const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks): see launch_fwd
+  const BlockSeq bs = key_seq_of_block<kDq>(a);   // grid (H, B, blocks): see launch_fwd
   const int b = bs.b, h = bs.h;
   SeqInfo s;
   s.start = bs.start;
@@ -2136,6 +2182,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const int n0 = bs.z * kBM;   // earliest key blocks (seen by most queries) first
   if (n0 >= s.L || xch_other_chunk(g, b, h)) return;
   const XchUnit xu = xch_unit(g, b, h, s.L);
+  const QRows qr = q_rows_of<kDq>(a, b, s);   // rows of q / dout (kDq: fewer than keys, at the positions qr.qoff + r)
+  if constexpr (kDq) { if (qr.qoff < 0) return; }   // more queries than keys: undefined (nothing is read or written for the sequence)
   s.has_ctx = a.num_contexts != nullptr;
   s.has_tgt = a.num_targets != nullptr;
   s.c = s.has_ctx ? a.num_contexts[b] : 0;
@@ -2154,8 +2202,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const int key_iend = (s.has_tgt && kj >= s.hlen) ? s.hlen + ((kj - s.hlen) / a.group + 1) * a.group : 0x7fffffff;
   const int ctx_end = s.has_ctx ? s.c : 0;
 
-  const uint16_t* qbase = a.q + (int64_t)s.start * a.q_row + (int64_t)h * a.q_head;
-  const uint16_t* dobase = g.dout + (int64_t)s.start * g.do_row + (int64_t)h * g.do_head;
+  const uint16_t* qbase = a.q + (int64_t)(kDq ? qr.qstart : s.start) * a.q_row + (int64_t)h * a.q_head;
+  const uint16_t* dobase = g.dout + (int64_t)(kDq ? qr.qstart : s.start) * g.do_row + (int64_t)h * g.do_head;
   // K / V fragments of the wave's 32 keys.  Keys beyond the sequence read a clamped row: kj < L is part of the mask.
   bf16x8_t kf[D / 16], vf[kDK ? D / 16 : 1];
   load_own_frags<D>(kf, a.k + (int64_t)s.start * a.k_row + (int64_t)h * a.k_head, a.k_row, kj, s.L, hi);
@@ -2175,7 +2223,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const float c_ds = a.alpha * a.inv_scale;  // dS = dP * c_ds * sigmoid * (1 + x (1 - sigmoid))
   // query tiles that can see this key block: the tiles holding contextual rows (they see all history keys), then
   // from the tile containing row n0 on (causal); everything (non causal)
-  const KvSpan span = kv_span(a, s, n0, BQ);
+  KvSpan span = kv_span(a, s, n0, BQ);
+  if constexpr (kDq) span = kv_span_dq(a, s, n0, BQ, qr);
   int jump = span.jump, c_end = span.c_end, i_lim = span.lim;
   if constexpr (kRab) {
     const int64_t kidx = func_kvis_index(s.start, b, n0);
@@ -2194,8 +2243,13 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   // network); only MODE 1, which has no other use for dO rows, fetches dO for that image alone
   RowTile<D, BQ> q_rows, do_rows;
   auto fetch_all = [&](int i) {
-    q_rows.fetch(qbase, a.q_row, i, s.L);
-    do_rows.fetch(dobase, g.do_row, i, s.L);
+    if constexpr (kDq) {
+      q_rows.fetch(qbase, a.q_row, i, qr.Lq);
+      do_rows.fetch(dobase, g.do_row, i, qr.Lq);
+    } else {
+      q_rows.fetch(qbase, a.q_row, i, s.L);
+      do_rows.fetch(dobase, g.do_row, i, s.L);
+    }
   };
   // kPre: small head dims run several waves per SIMD, which hides the staging latency better than holding a tile in
   // registers does (the prefetch registers would halve the occupancy); d = 256 runs one wave per SIMD and prefetches
@@ -2212,10 +2266,11 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
     TICK(t1);
     if (!kPre) fetch_all(i0);
     TICK(t1b);
-    q_rows.commit(Qs, i0, s.L);
-    if (kDK) do_rows.commit(dOs, i0, s.L);
-    if (kDK) q_rows.commit_tr(Qt, i0, s.L);
-    if (kDV) do_rows.commit_tr(dOt, i0, s.L);
+    const int q_len = kDq ? qr.Lq : s.L;
+    q_rows.commit(Qs, i0, q_len);
+    if (kDK) do_rows.commit(dOs, i0, q_len);
+    if (kDK) q_rows.commit_tr(Qt, i0, q_len);
+    if (kDV) do_rows.commit_tr(dOt, i0, q_len);
     if (kDV) pin_agpr(acc_dv);
     if (kDK) pin_agpr(acc_dk);
     TICK(t2);
@@ -2229,6 +2284,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
     if (kDK) pin_agpr(acc_dk);
     TACC(0, t0, t1); TACC(1, t1, t1b); TACC(2, t1b, t2); TACC(3, t2, t3);
     if (!wave_live) continue;
+    const int p0 = kDq ? i0 + qr.qoff : i0;   // absolute position of the step's first row
     TICK(t4);
     // GEMM 1 / 2: S[q x keys] = Q K^T, dP[q x keys] = dO V^T (A from LDS rows, B = register fragments)
     f32x16_t acc_s[NT], acc_p[kDK ? NT : 1];
@@ -2291,9 +2347,9 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
           for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) {
-              const int qi = i0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+              const int qi = p0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
               if (qi < s.L && !(s.has_ctx && qi < s.c && kj < s.hlen) &&
-                  !func_sees(a.func + (int64_t)h * a.func_h + s.start + qi, a.func_p, a.n_func, kj)) acc_s[t][rr] += a.func_neg;
+                  !func_sees(a.func + (int64_t)h * a.func_h + qr.qstart + (qi - qr.qoff), a.func_p, a.n_func, kj)) acc_s[t][rr] += a.func_neg;
             }
         }
       } else
@@ -2303,7 +2359,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
         for (int t = 0; t < NT; ++t)
 #pragma unroll
           for (int rr = 0; rr < 16; ++rr) {
-            const int qi = i0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+            const int qi = p0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
             if (qi < s.L) acc_s[t][rr] += bf16_bits_to_f32(col[(int64_t)qi * a.rab_r]);
           }
       }
@@ -2328,7 +2384,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             const int rr = r + u;
-            const int qi = i0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+            const int qi = p0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
             bool ok = true;
             if constexpr (kMask == 1) ok = kj <= qi;
             else if constexpr (kMask == 2) ok = kj < s.L;
@@ -2349,7 +2405,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
             if (g.drab && kj < s.L) {
 #pragma unroll
               for (int u = 0; u < 2; ++u) {
-                const int qi = i0 + 32 * t + ((r + u) & 3) + 8 * ((r + u) >> 2) + 4 * hi;
+                const int qi = p0 + 32 * t + ((r + u) & 3) + 8 * ((r + u) >> 2) + 4 * hi;
                 if (qi < s.L)
                   g.drab[(int64_t)b * g.drab_b + (int64_t)h * g.drab_h + (int64_t)qi * g.drab_r + kj] = (uint16_t)(sk[r >> 1] >> (16 * u));
               }
@@ -2379,7 +2435,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
     if (!plain) {
       if (s.wl >= 0 || s.wr >= 0) elementwise(std::integral_constant<int, 4>{}); else elementwise(std::integral_constant<int, 3>{});
     } else if (a.causal) {
-      if (key0 + 31 <= i0) elementwise(std::integral_constant<int, 0>{}); else elementwise(std::integral_constant<int, 1>{});
+      if (key0 + 31 <= p0) elementwise(std::integral_constant<int, 0>{}); else elementwise(std::integral_constant<int, 1>{});
     } else {
       if (key0 + 31 < s.L) elementwise(std::integral_constant<int, 0>{}); else elementwise(std::integral_constant<int, 2>{});
     }
@@ -2455,7 +2511,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
 }
 
 // pass B: one workgroup = 128 queries (32 per wave); loops over key tiles of BK keys -> dQ
-template <int D, int BK, bool kPre, bool kRab = false>
+// kDq (delta-q): the workgroup's rows are rows of q at the absolute positions qr.qoff + row; its key tiles are clipped from those
+template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false>
 __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
   constexpr int RS = D + 8, NT = BK / 32;
@@ -2465,14 +2522,16 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   uint16_t* Vs = Ks + BK * RS;       // [BK][RS]
   uint16_t* Kt = Vs + BK * RS;       // [BK][TRS]
 
-  const BlockSeq bs = seq_head_of_block(a);   // grid (H, B, blocks): see launch_fwd
+  const BlockSeq bs = key_seq_of_block<kDq>(a);   // grid (H, B, blocks): see launch_fwd
   const int b = bs.b, h = bs.h;
   SeqInfo s;
   s.start = bs.start;
   s.L = bs.end - s.start;
-  const int nblk = (s.L + kBM - 1) / kBM;
+  const QRows qr = q_rows_of<kDq>(a, b, s);
+  if constexpr (kDq) { if (qr.qoff < 0) return; }   // more queries than keys: undefined (nothing is read or written for the sequence)
+  const int nblk = (qr.Lq + kBM - 1) / kBM;
   if (bs.z >= nblk) return;
-  const int m0 = row_block_of_rank(bs.z, nblk, a, b) * kBM;
+  const int m0 = (kDq ? nblk - 1 - bs.z : row_block_of_rank(bs.z, nblk, a, b)) * kBM;
   s.has_ctx = a.num_contexts != nullptr;
   s.has_tgt = a.num_targets != nullptr;
   s.c = s.has_ctx ? a.num_contexts[b] : 0;
@@ -2480,22 +2539,26 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   s.wl = a.wl; s.wr = a.wr;
   const int lane = lane_id(), wv = threadIdx.x >> 6, hi = lane >> 5, l31 = lane & 31;
   const int qrow0 = m0 + 32 * wv;
-  const int qi = qrow0 + l31;
-  const bool wave_live = qrow0 < s.L;
-  int last_row = m0 + kBM - 1 < s.L - 1 ? m0 + kBM - 1 : s.L - 1;
+  const int qi = qrow0 + l31;                                 // row of q / dout / dq
+  const int pm0 = m0 + qr.qoff, pw0 = qrow0 + qr.qoff, pi = qi + qr.qoff;   // absolute positions of the block's / wave's first row, of the lane's row
+  const bool wave_live = qrow0 < qr.Lq;
+  int last_row = pm0 + kBM - 1 < s.L - 1 ? pm0 + kBM - 1 : s.L - 1;
   int n_end = s.L;
-  if (a.causal) { n_end = last_row + 1; if (s.has_ctx && m0 < s.c && s.hlen > n_end) n_end = s.hlen; }
-  int w_last = qrow0 + 31 < s.L - 1 ? qrow0 + 31 : s.L - 1;
+  if (a.causal) { n_end = last_row + 1; if (s.has_ctx && pm0 < s.c && s.hlen > n_end) n_end = s.hlen; }
+  int w_last = pw0 + 31 < s.L - 1 ? pw0 + 31 : s.L - 1;
   int w_end = s.L;
-  if (a.causal) { w_end = w_last + 1; if (s.has_ctx && qrow0 < s.c && s.hlen > w_end) w_end = s.hlen; }
+  if (a.causal) { w_end = w_last + 1; if (s.has_ctx && pw0 < s.c && s.hlen > w_end) w_end = s.hlen; }
   n_end = band_key_end(a, last_row, n_end);
   w_end = band_key_end(a, w_last, w_end);
-  int n_beg = band_key_begin(a, m0, BK), w_beg = band_key_begin(a, qrow0, BK);
+  int n_beg = band_key_begin(a, pm0, BK), w_beg = band_key_begin(a, pw0, BK);
+  // kDq: a wave of target rows only skips the target keys in front of its first row's group (the jump of hstu_bwd.h:93,126 from the query's side)
+  int w_gap_end = 0;
+  if constexpr (kDq) { if (s.has_tgt && pw0 >= s.hlen) w_gap_end = s.hlen + ((pw0 - s.hlen) / a.group) * a.group; }
   FuncExt wx{0x7fffffff, 0, 0x7fffffff, 0};       // (no functions: every tile "hits"; with functions and no skipping: no tile is "full")
   if constexpr (kRab) {
     if (a.func && a.wskip) {        // key tiles the block / the wave can reach, from the extents of their rows' functions (as in the forward)
       __shared__ int s_fx[3 * 4];
-      wx = func_ext_wave(func_ext_row(a, h, (int64_t)s.start + qi, qi < s.L, (s.has_ctx && qi < s.c) ? s.hlen : 0));
+      wx = func_ext_wave(func_ext_row(a, h, (int64_t)qr.qstart + qi, qi < qr.Lq, (s.has_ctx && pi < s.c) ? s.hlen : 0));
       const FuncExt bx = func_ext_block<4>(wx, wv, lane, s_fx);
       const int be = func_ext_end(bx), bb = func_ext_begin(bx), we = func_ext_end(wx), wb = func_ext_begin(wx);
       if (be < n_end) n_end = be;
@@ -2507,9 +2570,9 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
 
   // Q / dO fragments of the wave's 32 queries; rows beyond the sequence read a clamped row and are never stored
   bf16x8_t qf[D / 16], dof[D / 16];
-  load_own_frags<D>(qf, a.q + (int64_t)s.start * a.q_row + (int64_t)h * a.q_head, a.q_row, qi, s.L, hi);
-  load_own_frags<D>(dof, g.dout + (int64_t)s.start * g.do_row + (int64_t)h * g.do_head, g.do_row, qi, s.L, hi);
-  const RowMask rm = row_mask(qi < s.L ? qi : s.L - 1, s, a.causal, a.group);
+  load_own_frags<D>(qf, a.q + (int64_t)qr.qstart * a.q_row + (int64_t)h * a.q_head, a.q_row, qi, qr.Lq, hi);
+  load_own_frags<D>(dof, g.dout + (int64_t)qr.qstart * g.do_row + (int64_t)h * g.do_head, g.do_row, qi, qr.Lq, hi);
+  const RowMask rm = row_mask(pi < s.L ? pi : s.L - 1, s, a.causal, a.group);
   const float neg_alpha_log2e = -a.alpha * 1.4426950408889634f;
   const float c_ds = a.alpha * a.inv_scale;
   f32x16_t acc_dq[D / 32];
@@ -2539,6 +2602,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
     pin_agpr(acc_dq);
     if (!wave_live || n0 >= w_end || n0 < w_beg) continue;
     if constexpr (kRab) { if (!func_ext_hits(wx, n0, n0 + BK)) continue; }
+    if constexpr (kDq) { if (n0 >= s.hlen && n0 + BK <= w_gap_end) continue; }
     f32x16_t acc_s[NT], acc_p[NT];   // S^T, dP^T [keys x q]
     {
       constexpr int SLB = 4 / NT < D / 16 ? 4 / NT : D / 16;
@@ -2573,9 +2637,9 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
     fence_v(acc_s);
     fence_v(acc_p);
     if constexpr (kRab) {
-      if (a.func) { if (n0 + BK > wx.f0min) add_func_row<NT>(acc_s, a, h, (int64_t)s.start + qi, qi < s.L, n0, hi, s.L, (s.has_ctx && qi < s.c) ? s.hlen : 0); }
+      if (a.func) { if (n0 + BK > wx.f0min) add_func_row<NT>(acc_s, a, h, (int64_t)qr.qstart + qi, qi < qr.Lq, n0, hi, s.L, (s.has_ctx && pi < s.c) ? s.hlen : 0); }
       else {
-      const uint16_t* row = qi < s.L ? a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + (int64_t)qi * a.rab_r : nullptr;
+      const uint16_t* row = qi < qr.Lq ? a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + (int64_t)pi * a.rab_r : nullptr;
       add_rab_row<NT>(acc_s, row, n0, hi, s.L);
       }
     }
@@ -2624,8 +2688,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
     }
   }
   fence_a(acc_dq);
-  if (qi < s.L) {
-    uint16_t* dqp = g.dq + ((int64_t)(s.start + qi) * a.H + h) * D;
+  if (qi < qr.Lq) {
+    uint16_t* dqp = g.dq + ((int64_t)(qr.qstart + qi) * a.H + h) * D;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -3596,27 +3660,27 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
   if (kj < s.L) store_acc_rows<D>(acc_dk, g.dk + ((int64_t)(s.start + kj) * a.H + h) * D, hi);
 }
 
-template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false>
+template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
 static void launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;
   const size_t timg = (size_t)BQ * TrStride<D>::value;
   const size_t smem = (size_t)(BQ * (D + 8) + (kDK ? BQ * (D + 8) + timg : 0) + (kDV ? timg : 0)) * sizeof(uint16_t);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  hipLaunchKernelGGL((hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab>), grid, dim3(256), smem, stream, g);
+  hipLaunchKernelGGL((hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>), grid, dim3(256), smem, stream, g);
 }
-template <int D, int BK, bool kPre, bool kRab = false>
+template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false>
 static void launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem_q = (size_t)(2 * BK * (D + 8) + BK * TrStride<D>::value) * sizeof(uint16_t);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_q_kernel<D, BK, kPre, kRab>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
     attr_set = true;
   }
-  hipLaunchKernelGGL((hstu_bwd_q_kernel<D, BK, kPre, kRab>), grid, dim3(256), smem_q, stream, g);
+  hipLaunchKernelGGL((hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>), grid, dim3(256), smem_q, stream, g);
 }
 
 template <int D>   // (head dim 128; 256 takes launch_bwd_x8)
@@ -3720,6 +3784,25 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
     if (g.ds_ws) launch_bwd_q_ds<D>(g, grid, stream);
     else launch_bwd_q<D, 64, false>(g, grid, stream);
   }
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
+}
+
+// Delta-q backward (mi355_hstu_attn_bwd_kv): the recomputing passes with kDq -- the dV / dK pass(es) over grids of key blocks, the
+// dQ pass over a grid of query-row blocks; the step sizes per head dim are those launch_bwd uses without the exchange.
+template <int D, bool kRab>
+static int launch_bwd_dq(BwdAttnArgs g, int B, int max_q, int max_k, hipStream_t stream) {
+  const dim3 gk(g.f.H, B, (max_k + kBM - 1) / kBM), gq(g.f.H, B, (max_q + kBM - 1) / kBM);
+  g.ds_ws = g.p_ws = nullptr;
+  g.bq_kv = 64;
+  constexpr bool kPre = D >= 256 && !kRab;   // (as launch_bwd: only the unbiased 256 passes prefetch)
+  if constexpr (D >= 128) {
+    launch_bwd_kv<D, 64, 1, kPre, false, kRab, true>(g, gk, stream);
+    launch_bwd_kv<D, (D >= 256 && !kRab) ? 64 : 32, 2, false, false, kRab, true>(g, gk, stream);
+  } else {
+    launch_bwd_kv<D, 64, 0, false, false, kRab, true>(g, gk, stream);
+  }
+  if (max_q > 0) launch_bwd_q<D, D >= 256 ? 32 : 64, kPre, kRab, true>(g, gq, stream);   // (no queries at all: dK = dV = 0 is the whole result)
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }
@@ -4265,6 +4348,71 @@ int HSTU_FN(mi355_hstu_attn_bwd_rab)(const void* dout, const void* q, const void
   tl_rab = RabCall{};
   tl_wl = tl_wr = -1;
   return rc;
+}
+
+// Delta-q backward (hstu_bwd.h:98: actual_seqlen_offset = actual_seqlen_k - actual_seqlen_q in every tile bound and mask; the
+// reference's kernel tests differentiate such calls, corelib/hstu/test.py:667-720).  The queries of sequence b -- rows
+// cu_seqlens_q[b] .. of q / dout / dq -- are the LAST Lq of its Lk keys (rows cu_seqlens_k[b] .. of k / v / dk / dv), every mask and
+// the bias are taken at the absolute positions Lk - Lq + r.  Mask as window_size: (-1, 0) causal (contextual / target rows
+// allowed), (-1, -1) full, otherwise a local window.  rab / drab nullable, [batch][heads or 1 / heads][max_seqlen_k][max_seqlen_k];
+// drab zero-filled by the caller (its rows in front of a sequence's first query stay zero).  The recomputing passes, no scratch;
+// every row of dq / dk / dv is written (keys no query reaches: zeros).  Lq > Lk in a sequence is visible on the device only and
+// undefined, as in the forward: the passes touch nothing of that sequence and its gradient rows stay unwritten.
+int HSTU_FN(mi355_hstu_attn_bwd_kv)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                           int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                           int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                           const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads,
+                           int64_t head_dim, int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                           const int32_t* num_targets, int64_t target_group_size, int64_t window_left, int64_t window_right,
+                           float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride, int64_t rab_head_stride,
+                           int64_t rab_row_stride, void* drab, int64_t drab_batch_stride, int64_t drab_head_stride,
+                           int64_t drab_row_stride, hipStream_t stream) {
+  MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
+                  "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
+  MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
+  MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
+  MI355_CHECK_ARG(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && do_row_stride % 8 == 0 &&
+                      q_head_stride % 8 == 0 && k_head_stride % 8 == 0 && v_head_stride % 8 == 0 && do_head_stride % 8 == 0,
+                  "q/k/v/dout strides must be multiples of 8 elements (16-byte rows)");
+  MI355_CHECK_ARG(batch == 0 || (cu_seqlens_q && cu_seqlens_k), "cu_seqlens_q and cu_seqlens_k are required");
+  MI355_CHECK_ARG(max_seqlen_q >= 0 && max_seqlen_q <= max_seqlen_k, "the queries are the last rows of the keys: max_seqlen_q <= max_seqlen_k (Lq <= Lk)");
+  MI355_CHECK_ARG(rab == nullptr || rab_row_stride >= max_seqlen_k, "rab must be [batch][heads or 1][max_seqlen_k][max_seqlen_k]");
+  MI355_CHECK_ARG(drab == nullptr || (rab != nullptr && drab_row_stride >= max_seqlen_k && drab_head_stride > 0),
+                  "drab needs rab and must hold one [max_seqlen_k][max_seqlen_k] matrix per head");
+  int causal = 0;
+  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
+  BwdAttnArgs g{};
+  AttnArgs& a = g.f;
+  a.wl = tl_wl; a.wr = tl_wr;
+  tl_wl = tl_wr = -1;
+  if (batch == 0 || max_seqlen_k == 0) return MI355_OK;
+  a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = nullptr;
+  a.q_row = q_row_stride; a.k_row = k_row_stride; a.v_row = v_row_stride; a.o_row = 0;
+  a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = 0;
+  a.cu_seqlens = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k; a.num_contexts = num_contexts; a.num_targets = num_targets;
+  a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
+  a.wskip = window_skip(); a.rot = 0; a.colmajor = 0; a.max_len = (int)max_seqlen_k;
+  a.rab = (const uint16_t*)rab; a.rab_b = rab_batch_stride; a.rab_h = rab_head_stride; a.rab_r = rab_row_stride;
+  a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
+  g.dout = (const uint16_t*)dout; g.do_row = do_row_stride; g.do_head = do_head_stride;
+  g.dq = (uint16_t*)dq; g.dk = (uint16_t*)dk; g.dv = (uint16_t*)dv;
+  g.ng = (int)((max_seqlen_k + 31) / 32);
+  g.drab = (uint16_t*)drab; g.drab_b = drab_batch_stride; g.drab_h = drab_head_stride; g.drab_r = drab_row_stride;
+  const int B = (int)batch, mq = (int)max_seqlen_q, mk = (int)max_seqlen_k;
+  if (rab) {
+    switch (head_dim) {
+      case 32: return launch_bwd_dq<32, true>(g, B, mq, mk, stream);
+      case 64: return launch_bwd_dq<64, true>(g, B, mq, mk, stream);
+      case 128: return launch_bwd_dq<128, true>(g, B, mq, mk, stream);
+      default: return launch_bwd_dq<256, true>(g, B, mq, mk, stream);
+    }
+  }
+  switch (head_dim) {
+    case 32: return launch_bwd_dq<32, false>(g, B, mq, mk, stream);
+    case 64: return launch_bwd_dq<64, false>(g, B, mq, mk, stream);
+    case 128: return launch_bwd_dq<128, false>(g, B, mq, mk, stream);
+    default: return launch_bwd_dq<256, false>(g, B, mq, mk, stream);
+  }
 }
 
 // Arbitrary mask functions (`func` of hstu_attn_varlen_func; hstu_api.cpp:170-180, applied in hstu_fwd.h:139-145, 493-556) read INSIDE

@@ -8,8 +8,8 @@ What is implemented: HBM / host / hybrid / promoting-cache storage tiers, poolin
 dims for pooled mode, SGD / Adam / AdaGrad / row-wise AdaGrad fused in the backward, score strategies TIMESTAMP /
 STEP / CUSTOMIZED / LFU, train == eval for known keys, zeros for unknown keys in eval, first-touch insert + initialise
 in train, prefetch(), dump / load / export, frequency admission (`admit_strategy` + `admission_counter`).
-Table growth by rehash (init_capacity -> max_capacity, VMM value buffers) for HBM storage.  Not built: NO_EVICTION,
-external storage.
+Table growth by rehash (init_capacity -> max_capacity, VMM value buffers) for HBM storage; external storage behind the table
+is `external_storage.py`.  Not built: NO_EVICTION.
 """
 from __future__ import annotations
 

@@ -5,8 +5,10 @@ Mirrors `HstuAttnVarlenFunc` / `hstu_attn_varlen_func` of the reference
 examples/hstu/modules/hstu_attention.py:296-314): same argument meaning, same input checks
 (bf16 or fp16 q / k / v, int32 cu_seqlens / num_contexts / num_targets, head_dim in {32, 64, 128, 256},
 contextual / target masks require causal -- hstu_api.cpp:359-430).
-Inference extensions (forward only): cu_seqlens_k longer than cu_seqlens_q (delta-q) and the paged KV cache
-(kv_cache / page_offsets / page_ids / last_page_lens).
+Inference extensions: cu_seqlens_k longer than cu_seqlens_q (delta-q: the queries are the last Lq of a sequence's Lk keys) and the
+paged KV cache (kv_cache / page_offsets / page_ids / last_page_lens).  A cache-less delta-q call is differentiable like a training
+call -- plain, window and rab masks, drab included (HstuAttnDeltaQFunc over mi355_hstu_attn_bwd_kv; hstu_bwd.h:98 carries the
+same offset) --; the paged cache, `func` over delta-q keys and FP8 are forward only.
 Arbitrary mask functions (`func`, hstu_api.cpp:170-180) are read INSIDE the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func: no mask
 tensor exists), forward and backward, with any other mask -- contextual rows keep their view of the history, as in the
 reference's kernels (hstu_fwd.h:519-524) --, over delta-q / paged keys too.  Next to a relative bias they are added to it as a
@@ -52,6 +54,9 @@ N.register_signatures({
     "mi355_hstu_attn_fwd_kv_rab": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64,
                                    c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
                                    c_p, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_attn_bwd_kv": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p,
+                               c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
+                               c_p, c_i64, c_i64, c_i64, c_p],
     "mi355_hstu_attn_fwd_kv_func": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64,
                                     c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
                                     c_f, c_p, c_p, c_p, c_p, c_i64, c_p],
@@ -63,8 +68,8 @@ N.register_signatures({
 }, {"mi355_hstu_attn_bwd_workspace_bytes": c_i64, "mi355_hstu_attn_bwd_ds_bytes": c_i64,
     "mi355_hstu_attn_bwd_ds_bytes_capped": c_i64, "mi355_hstu_attn_bwd_hint_tokens": None,
     "mi355_hstu_attn_fwd_hint_tokens": None, "mi355_hstu_attn_fwd_hint_tokens_f16": None})
-# the fp16-operand twins of the seven type-specific entry points (same argument lists)
-_TYPED = ("mi355_hstu_attn_fwd_hint_tokens", "mi355_hstu_attn_fwd", "mi355_hstu_attn_fwd_kv", "mi355_hstu_attn_fwd_kv_window", "mi355_hstu_attn_fwd_kv_rab", "mi355_hstu_attn_bwd", "mi355_hstu_attn_fwd_window",
+# the fp16-operand twins of the type-specific entry points (same argument lists)
+_TYPED = ("mi355_hstu_attn_bwd_kv", "mi355_hstu_attn_fwd_hint_tokens", "mi355_hstu_attn_fwd", "mi355_hstu_attn_fwd_kv", "mi355_hstu_attn_fwd_kv_window", "mi355_hstu_attn_fwd_kv_rab", "mi355_hstu_attn_bwd", "mi355_hstu_attn_fwd_window",
           "mi355_hstu_attn_bwd_window", "mi355_hstu_attn_fwd_rab", "mi355_hstu_attn_bwd_rab", "mi355_hstu_attn_fwd_kv_func",
           "mi355_hstu_attn_bwd_func")
 N.register_signatures({n + "_f16": N.signature_of(n) for n in _TYPED})
@@ -368,6 +373,67 @@ def hstu_varlen_bwd_rab(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, n
     return dq, dk, dv, drab
 
 
+def hstu_varlen_bwd_kv(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scaling_seqlen, num_contexts,
+                       num_targets, target_group_size, wl, wr, alpha, rab=None, has_drab=False):
+    """Raw backward of a cache-less delta-q call (mi355_hstu_attn_bwd_kv): the queries of a sequence are the last Lq of its Lk
+    keys, masks and bias at the absolute positions Lk - Lq + r.  (wl, wr) as window_size: (-1, 0) causal, (-1, -1) full, else a
+    local window.  Returns (dq [total_q, H, d], dk, dv [total_k, H, d], drab or None); drab has the shape of rab, summed over the
+    heads in fp32 when rab has one shared head (as hstu_varlen_bwd_rab), zero in the rows in front of a sequence's first query."""
+    H, D = q.shape[1], q.shape[2]
+    if has_drab and rab is None:
+        raise ValueError("has_drab needs rab")
+    dout = dout.contiguous() if dout.stride(-1) != 1 else dout
+    dq = torch.empty((q.shape[0], H, D), dtype=q.dtype, device=q.device)
+    dk = torch.empty((k.shape[0], H, D), dtype=q.dtype, device=q.device)
+    dv = torch.empty_like(dk)
+    B = cu_seqlens_q.numel() - 1
+    rb, rh, rr = _rab_strides(rab, H) if rab is not None else (0, 0, 0)
+    N = int(max_seqlen_k)
+    drab = torch.zeros((B, H, N, N), dtype=q.dtype, device=q.device) if has_drab else None
+    ds = (drab.stride(0), drab.stride(1), drab.stride(2)) if has_drab else (0, 0, 0)
+    check(_fn("mi355_hstu_attn_bwd_kv", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
+                                           v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
+                                           ptr(cu_seqlens_q), ptr(cu_seqlens_k), B, H, D, int(max_seqlen_q), N, ptr(num_contexts),
+                                           ptr(num_targets), int(target_group_size), int(wl), int(wr), c_f(alpha),
+                                           c_f(float(scaling_seqlen)), ptr(rab), rb, rh, rr, ptr(drab), ds[0], ds[1], ds[2],
+                                           stream()), "hstu_attn_bwd_kv")
+    if has_drab and rab.shape[1] == 1 and H > 1:
+        drab = drab.float().sum(1, keepdim=True).to(q.dtype)
+    return dq, dk, dv, drab
+
+
+class HstuAttnDeltaQFunc(torch.autograd.Function):
+    """cache-less delta-q attention (cu_seqlens_k longer than cu_seqlens_q) with gradients: plain, window and rab masks; rab
+    (nullable) receives a gradient when has_drab (corelib/hstu/test.py:667-720 differentiates the same calls)"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rab, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scaling_seqlen, num_contexts, num_targets,
+                target_group_size, wl, wr, alpha, has_drab):
+        local = not (wl == -1 and wr in (-1, 0))
+        out = hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, scaling_seqlen, num_contexts, num_targets,
+                                 target_group_size, wr == 0, alpha, window=(wl, wr) if local else None, rab=rab,
+                                 max_seqlen_k=max_seqlen_k)
+        ctx.save_for_backward(q, k, v, rab, cu_seqlens_q, cu_seqlens_k, num_contexts, num_targets)
+        ctx.meta = (max_seqlen_q, max_seqlen_k, scaling_seqlen, target_group_size, wl, wr, alpha, has_drab)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, rab, cu_q, cu_k, nc, nt = ctx.saved_tensors
+        max_q, max_k, scaling, g, wl, wr, alpha, has_drab = ctx.meta
+        dq, dk, dv, drab = hstu_varlen_bwd_kv(dout, q, k, v, cu_q, cu_k, max_q, max_k, scaling, nc, nt, g, wl, wr, alpha, rab, has_drab)
+        return dq, dk, dv, drab, None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _delta_q_autograd(q, k, v, rab, kv_cache):
+    """does a delta-q / paged-KV call take the differentiable path?  Raises where a gradient is asked for and none exists."""
+    needs = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (rab is not None and rab.requires_grad))
+    if needs and kv_cache is not None:
+        raise NotImplementedError("attention over a paged KV cache is forward only: no gradient is defined into the page table "
+                                  "(pass the keys contiguously with cu_seqlens_k for a differentiable delta-q call)")
+    return needs
+
+
 _FUNC_NEG = {}
 _FUNC_DENSE = __import__("os").environ.get("MI355_HSTU_FUNC_DENSE", "0") == "1"
 
@@ -522,7 +588,8 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
         if not _FUNC_DENSE:
             if not same:   # inference (delta-q keys and / or the paged cache): forward only
                 if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-                    raise NotImplementedError("delta-q / paged-KV attention is forward only (as in the reference's inference path)")
+                    raise NotImplementedError("func over delta-q keys or a paged KV cache is forward only (the delta-q backward "
+                                              "takes the plain, window and rab masks)")
                 return hstu_varlen_fwd_func(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), scaling_seqlen,
                                             num_contexts, num_targets, int(target_group_size), wl, wr, float(alpha), func, kv_cache,
                                             page_offsets, page_ids, last_page_lens)
@@ -540,9 +607,16 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
     if rab is not None:
         if rab.shape[-1] != int(max_seqlen_k):
             raise RuntimeError("rab must be (batch, nheads or 1, max_seqlen_k, max_seqlen_k)")
-        if not same:   # inference (delta-q keys and / or the paged cache) with a bias: forward only
-            if has_drab or (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or rab.requires_grad)):
-                raise NotImplementedError("delta-q / paged-KV attention is forward only (as in the reference's inference path)")
+        if not same:   # delta-q keys and / or the paged cache with a bias
+            if func is not None and (has_drab or (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or rab.requires_grad))):
+                raise NotImplementedError("func over delta-q keys or a paged KV cache is forward only (the delta-q backward "
+                                          "takes the plain, window and rab masks)")
+            if has_drab and kv_cache is not None:
+                raise NotImplementedError("has_drab over a paged KV cache: attention over the cache is forward only")
+            if _delta_q_autograd(q, k, v, rab, kv_cache) or has_drab:
+                return HstuAttnDeltaQFunc.apply(q, k, v, rab, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k),
+                                                scaling_seqlen, num_contexts, num_targets, int(target_group_size), wl, wr,
+                                                float(alpha), bool(has_drab))
             local = not (wl == -1 and wr in (-1, 0))
             return hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), scaling_seqlen, num_contexts, num_targets,
                                       int(target_group_size), causal, float(alpha), kv_cache, page_offsets, page_ids, last_page_lens,
@@ -553,16 +627,19 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
                                      int(target_group_size), wl, wr, float(alpha), bool(has_drab))
     if not (wl == -1 and wr in (-1, 0)):
         if not same:
-            # inference under a local window (delta-q keys and / or the paged cache): forward only, as the plain inference path
-            if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-                raise NotImplementedError("delta-q / paged-KV attention is forward only (as in the reference's inference path)")
+            # a local window over delta-q keys and / or the paged cache (the cache: forward only)
+            if _delta_q_autograd(q, k, v, None, kv_cache):
+                return HstuAttnDeltaQFunc.apply(q, k, v, None, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k),
+                                                scaling_seqlen, None, None, 1, wl, wr, float(alpha), False)
             return hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), scaling_seqlen, None, None, 1,
                                       wr == 0, float(alpha), kv_cache, page_offsets, page_ids, last_page_lens, window=(wl, wr))
         return HstuAttnWindowFunc.apply(q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, wl, wr, float(alpha))
     if kv_cache is not None or not same:
-        # inference: keys longer than the queries and / or history keys in the paged cache; no backward
-        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-            raise NotImplementedError("delta-q / paged-KV attention is forward only (as in the reference's inference path)")
+        # keys longer than the queries and / or history keys in the paged cache (the cache: forward only)
+        if _delta_q_autograd(q, k, v, None, kv_cache):
+            return HstuAttnDeltaQFunc.apply(q, k, v, None, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k),
+                                            scaling_seqlen, num_contexts, num_targets, int(target_group_size), wl, wr,
+                                            float(alpha), False)
         return hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), scaling_seqlen, num_contexts,
                                   num_targets, int(target_group_size), causal, float(alpha), kv_cache, page_offsets,
                                   page_ids, last_page_lens)

@@ -8,7 +8,9 @@ positional order of those call sites, backed by the gfx950 kernels, plus Meta ke
 no kernel for (seqused, fp8 quantisation) must be None / default; the ops raise otherwise.  `func` (arbitrary mask functions)
 is read inside the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func); next to a relative bias it is added to it as a 0 / -1e9 bias
 (hstu_attn_interface.func_mask_bias).
-`window_size_left / right` with a finite side run the local-window kernels, `rab` / `has_drab` the bias kernels."""
+`window_size_left / right` with a finite side run the local-window kernels, `rab` / `has_drab` the bias kernels.
+These raw ops stay self-attention only (cu_seqlens_q == cu_seqlens_k): the fused layer never calls them otherwise.  Delta-q calls,
+forward and backward, go through `hstu_attn_varlen_func` / `hstu.hstu_varlen_bwd_kv`."""
 import torch
 
 from .hstu_fp8 import _FP8_TYPES
