@@ -810,6 +810,17 @@ int64_t mi355_hstu_attn_bwd_ds_bytes_capped(int64_t batch, int64_t num_heads, in
 /* total tokens of the NEXT mi355_hstu_attn_bwd call on this thread (its signature is the reference's hstu_varlen_bwd and
  * does not carry them): bounds the number of chunk passes; optional. */
 void mi355_hstu_attn_bwd_hint_tokens(int64_t total_tokens);
+/* row and head strides, in elements, of dq, dk, dv of the NEXT backward call on this thread: any of mi355_hstu_attn_bwd,
+ * _bwd_window, _bwd_rab, _bwd_func, _bwd_kv and their _f16 twins (one binding for both operand types), whose signatures are the
+ * reference's and take the three gradients as contiguous [total, H, d].  The callers this serves hand the kernel views into one
+ * buffer: the fused layer's duvqk split (examples/hstu/ops/fused_hstu_op.py:932-1006, row stride (2 dl + 2 da) H) and the packed
+ * dqkv[:, i] of hstu_attn_qkvpacked_func (corelib/hstu/hstu_attn/hstu_attn_interface.py:378-388, row stride 3 H d).  The gradients
+ * are stored at base + row * row_stride + head * head_stride, the last dimension contiguous; rows that receive zeros (keys no
+ * query reaches, a sequence without queries) receive them there.  That call takes the binding on entry: it is gone whether the
+ * call succeeds, returns early (batch == 0) or fails an argument check.  Checked by that call, MI355_EINVAL otherwise: every
+ * stride a multiple of 8 elements below 2^31, head strides >= head_dim.  Nothing bound: H d and d. */
+void mi355_hstu_attn_bwd_bind_grad_strides(int64_t dq_row_stride, int64_t dq_head_stride, int64_t dk_row_stride,
+                                           int64_t dk_head_stride, int64_t dv_row_stride, int64_t dv_head_stride);
 /* rows of q of the NEXT mi355_hstu_attn_fwd / _fwd_kv / _fwd_window call on this thread (optional): batch x max_seqlen rows
  * = a dense batch, which the head-dim-256 forward runs with two row blocks (the z-th heaviest and z-th lightest of a column)
  * per workgroup.  The fp16 entry points have their own hint (suffix _f16). */

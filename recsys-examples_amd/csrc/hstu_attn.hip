@@ -1861,7 +1861,7 @@ __device__ __forceinline__ void load_own_frags(bf16x8_t (&f)[D / 16], const uint
 struct BwdAttnArgs {
   AttnArgs f;                  // q, k, v (+ strides); f.out unused
   const uint16_t* dout; int64_t do_row, do_head;
-  uint16_t* dq; uint16_t* dk; uint16_t* dv;   // contiguous [T, H, D]
+  uint16_t* dq; uint16_t* dk; uint16_t* dv;   // [T, H, D] by the row / head strides at the end of this struct
   // dS exchange between the dK pass and the dQ pass (nullable): 32 x 32 sub-tiles of dS in the dK pass's register layout
   // (lane = key, 16 query rows per lane: 32 bytes per lane, 2 KB per sub-tile), indexed [b][h][key group][query group]
   uint16_t* ds_ws;
@@ -1884,6 +1884,10 @@ struct BwdAttnArgs {
   // (hstu_func_kvis_kernel, launched in front of the passes); NULL: every query tile is visited
   const int2* func_kvis; int64_t func_kvis_h;
   const int4* func_gext;       // per 32-row group: {smallest prefix, largest prefix, band hull}; 4 func_kvis_h entries per function set
+  // row / head strides of dq, dk, dv in elements (last dim contiguous): H D and D unless the caller bound others
+  // (mi355_hstu_attn_bwd_bind_grad_strides).  32 bits each -- six scalar registers, not twelve, next to full kernels -- and LAST:
+  // the epilogues alone read them, and every field the main loops read keeps its place in the argument block
+  int dq_row, dq_head, dk_row, dk_head, dv_row, dv_head;
 };
 // where a (sequence, head) unit's sub-tiles live: read ONCE per block (inside the step loops a load of the plan could not be
 // hoisted over the stores and cost a scalar-load latency per step: +27 % on a jagged batch)
@@ -2489,8 +2493,8 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   }
 #endif
   if (kj < s.L) {
-    uint16_t* dvp = g.dv + ((int64_t)(s.start + kj) * a.H + h) * D;
-    uint16_t* dkp = g.dk + ((int64_t)(s.start + kj) * a.H + h) * D;
+    uint16_t* dvp = g.dv + (int64_t)(s.start + kj) * g.dv_row + (int64_t)h * g.dv_head;
+    uint16_t* dkp = g.dk + (int64_t)(s.start + kj) * g.dk_row + (int64_t)h * g.dk_head;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -2689,7 +2693,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   }
   fence_a(acc_dq);
   if (qi < qr.Lq) {
-    uint16_t* dqp = g.dq + ((int64_t)(qr.qstart + qi) * a.H + h) * D;
+    uint16_t* dqp = g.dq + (int64_t)(qr.qstart + qi) * g.dq_row + (int64_t)h * g.dq_head;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -2829,7 +2833,7 @@ __global__ void __launch_bounds__(256, HSTU_XOCC) hstu_bwd_q_ds_kernel(BwdAttnAr
   }
   fence_a(acc_dq);
   if (qi < s.L) {
-    uint16_t* dqp = g.dq + ((int64_t)(s.start + qi) * a.H + h) * D;
+    uint16_t* dqp = g.dq + (int64_t)(s.start + qi) * g.dq_row + (int64_t)h * g.dq_head;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -2940,7 +2944,7 @@ __global__ void __launch_bounds__(256, HSTU_XOCC) hstu_bwd_v_p_kernel(BwdAttnArg
   }
   fence_a(acc_dv);
   if (kj < s.L) {
-    uint16_t* dvp = g.dv + ((int64_t)(s.start + kj) * a.H + h) * D;
+    uint16_t* dvp = g.dv + (int64_t)(s.start + kj) * g.dv_row + (int64_t)h * g.dv_head;
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -3140,7 +3144,7 @@ __device__ __forceinline__ void hstu_bwd_v_p8_body(const BwdAttnArgs& g, unsigne
     step(std::integral_constant<int, 1>{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (kj < s.L) store_acc_rows<D>(acc, g.dv + ((int64_t)(s.start + kj) * a.H + h) * D, hi);
+  if (kj < s.L) store_acc_rows<D>(acc, g.dv + (int64_t)(s.start + kj) * g.dv_row + (int64_t)h * g.dv_head, hi);
 }
 
 // dQ from the stored dS, 128 query rows per workgroup (the layout juggling of hstu_bwd_q_ds_kernel: the 2 KB sub-tile goes
@@ -3291,7 +3295,7 @@ __device__ __forceinline__ void hstu_bwd_q_ds8_body(const BwdAttnArgs& g, unsign
     step(std::integral_constant<int, 1>{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (qi < s.L) store_acc_rows<D>(acc, g.dq + ((int64_t)(s.start + qi) * a.H + h) * D, hi);
+  if (qi < s.L) store_acc_rows<D>(acc, g.dq + (int64_t)(s.start + qi) * g.dq_row + (int64_t)h * g.dq_head, hi);
 }
 
 // Round 6: the two one-GEMM passes in ONE launch -- they are independent (dV reads P, dQ reads dS, both written by the dK pass) and
@@ -3657,7 +3661,7 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
 #if HSTU_TIMING
   t_dump();
 #endif
-  if (kj < s.L) store_acc_rows<D>(acc_dk, g.dk + ((int64_t)(s.start + kj) * a.H + h) * D, hi);
+  if (kj < s.L) store_acc_rows<D>(acc_dk, g.dk + (int64_t)(s.start + kj) * g.dk_row + (int64_t)h * g.dk_head, hi);
 }
 
 template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
@@ -3929,6 +3933,25 @@ static int64_t xch_tiles_bound(int64_t batch, int64_t num_heads, int64_t ng, int
   return num_heads * (jag < dense ? jag : dense);
 }
 extern "C" int64_t mi355_hstu_attn_bwd_take_hint_(void);
+extern "C" int mi355_hstu_attn_bwd_take_grad_strides_(int64_t* strides);
+// The strides of dq / dk / dv for the backward entered on this thread: what mi355_hstu_attn_bwd_bind_grad_strides left (taken, so
+// the binding is gone from here on whatever the call does next), else the contiguous [T, H, D] layout.
+struct GradStrides { int64_t s[6]; bool bound; };
+static GradStrides take_grad_strides(int64_t num_heads, int64_t head_dim) {
+  GradStrides g;
+  g.bound = mi355_hstu_attn_bwd_take_grad_strides_(g.s) != 0;
+  if (!g.bound)
+    for (int i = 0; i < 6; i += 2) { g.s[i] = num_heads * head_dim; g.s[i + 1] = head_dim; }
+  return g;
+}
+static bool grad_strides_ok(const GradStrides& g, int64_t head_dim) {
+  for (int i = 0; i < 6; ++i)
+    if (g.s[i] % 8 != 0 || g.s[i] < 0 || g.s[i] > INT32_MAX || ((i & 1) && g.s[i] < head_dim)) return false;
+  return true;
+}
+// The entry points that check arguments of their own in front of mi355_hstu_attn_bwd hold one of these: a binding such a check
+// returned past is dropped on the way out (the inner call has taken it otherwise and this finds nothing).
+struct GradStridesDrop { ~GradStridesDrop() { int64_t s[6]; mi355_hstu_attn_bwd_take_grad_strides_(s); } };
 
 extern "C" {
 #if HSTU_TIMING && !HSTU_F16
@@ -4086,6 +4109,23 @@ int64_t mi355_hstu_attn_bwd_ds_bytes_capped(int64_t batch, int64_t num_heads, in
 static thread_local int64_t tl_bwd_tokens = 0;
 void mi355_hstu_attn_bwd_hint_tokens(int64_t total_tokens) { tl_bwd_tokens = total_tokens; }
 int64_t mi355_hstu_attn_bwd_take_hint_(void) { const int64_t t = tl_bwd_tokens; tl_bwd_tokens = 0; return t; }   // (internal: both translation units)
+// row / head strides, in elements, of dq, dk, dv of the NEXT backward call on this thread -- any of mi355_hstu_attn_bwd, _bwd_window,
+// _bwd_rab, _bwd_func, _bwd_kv and their _f16 twins, whose signatures (the reference's) take the three as contiguous.  That call
+// takes the binding on entry, in front of its argument checks: it never outlives the call, however the call ends.
+static thread_local int64_t tl_grad_strides[6];
+static thread_local bool tl_grad_bound = false;
+void mi355_hstu_attn_bwd_bind_grad_strides(int64_t dq_row_stride, int64_t dq_head_stride, int64_t dk_row_stride,
+                                           int64_t dk_head_stride, int64_t dv_row_stride, int64_t dv_head_stride) {
+  const int64_t s[6] = {dq_row_stride, dq_head_stride, dk_row_stride, dk_head_stride, dv_row_stride, dv_head_stride};
+  for (int i = 0; i < 6; ++i) tl_grad_strides[i] = s[i];
+  tl_grad_bound = true;
+}
+int mi355_hstu_attn_bwd_take_grad_strides_(int64_t* strides) {   // (internal: both translation units) 1 = there was a binding
+  const bool bound = tl_grad_bound;
+  tl_grad_bound = false;
+  if (bound) for (int i = 0; i < 6; ++i) strides[i] = tl_grad_strides[i];
+  return bound ? 1 : 0;
+}
 
 #endif
 
@@ -4100,15 +4140,19 @@ static int* plan_err_word() {
   return w;
 }
 
-// hstu_varlen_bwd (corelib/hstu/csrc/hstu_attn/hstu_api.cpp:525-719).  dq, dk, dv: contiguous bf16 [total, H, d].
+// hstu_varlen_bwd (corelib/hstu/csrc/hstu_attn/hstu_api.cpp:525-719).  dq, dk, dv: bf16 [total, H, d], contiguous unless
+// mi355_hstu_attn_bwd_bind_grad_strides gave this call their strides.
 int HSTU_FN(mi355_hstu_attn_bwd)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
                         int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
                         int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
                         const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
                         const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size, int causal,
                         float alpha, float scaling_seqlen, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const GradStrides gs = take_grad_strides(num_heads, head_dim);
   MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
                   "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
+  MI355_CHECK_ARG(grad_strides_ok(gs, head_dim),
+                  "bound dq/dk/dv strides must be multiples of 8 elements in [0, 2^31), the head strides >= head_dim");
   MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
   MI355_CHECK_ARG(causal || (!num_contexts && !num_targets), "contextual / target masks require causal attention");
   MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
@@ -4137,6 +4181,7 @@ int HSTU_FN(mi355_hstu_attn_bwd)(const void* dout, const void* q, const void* k,
   a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
   g.dout = (const uint16_t*)dout; g.do_row = do_row_stride; g.do_head = do_head_stride;
   g.dq = (uint16_t*)dq; g.dk = (uint16_t*)dk; g.dv = (uint16_t*)dv;
+  g.dq_row = (int)gs.s[0]; g.dq_head = (int)gs.s[1]; g.dk_row = (int)gs.s[2]; g.dk_head = (int)gs.s[3]; g.dv_row = (int)gs.s[4]; g.dv_head = (int)gs.s[5];
   g.ds_ws = nullptr; g.ng = (int)((max_seqlen + 31) / 32); g.bq_kv = 32;
   g.drab = tl_rab.drab; g.drab_b = tl_rab.db; g.drab_h = tl_rab.dh; g.drab_r = tl_rab.dr;
   g.plan_base = nullptr; g.plan_chunk = nullptr; g.chunk = 0;
@@ -4256,6 +4301,7 @@ int HSTU_FN(mi355_hstu_attn_bwd_window)(const void* dout, const void* q, const v
                                const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim,
                                int64_t max_seqlen, int64_t window_left, int64_t window_right, float alpha,
                                float scaling_seqlen, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  GradStridesDrop drop_unreached_binding;
   MI355_CHECK_ARG(window_left >= -1 && window_right >= -1 && window_left < (1 << 30) && window_right < (1 << 30), "bad window");
   tl_wl = (int)window_left; tl_wr = window_right == 0 ? -1 : (int)window_right;
   const int rc = HSTU_FN(mi355_hstu_attn_bwd)(dout, q, k, v, dq, dk, dv, q_row_stride, k_row_stride, v_row_stride, do_row_stride,
@@ -4334,6 +4380,7 @@ int HSTU_FN(mi355_hstu_attn_bwd_rab)(const void* dout, const void* q, const void
                             int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
                             int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
                             int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream) {
+  GradStridesDrop drop_unreached_binding;
   MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen, "rab must be [batch][heads or 1][max_seqlen][max_seqlen]");
   MI355_CHECK_ARG(drab == nullptr || (drab_row_stride >= max_seqlen && drab_head_stride > 0),
                   "drab must hold one [max_seqlen][max_seqlen] matrix per head");
@@ -4367,8 +4414,11 @@ int HSTU_FN(mi355_hstu_attn_bwd_kv)(const void* dout, const void* q, const void*
                            float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride, int64_t rab_head_stride,
                            int64_t rab_row_stride, void* drab, int64_t drab_batch_stride, int64_t drab_head_stride,
                            int64_t drab_row_stride, hipStream_t stream) {
+  const GradStrides gs = take_grad_strides(num_heads, head_dim);
   MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
                   "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
+  MI355_CHECK_ARG(grad_strides_ok(gs, head_dim),
+                  "bound dq/dk/dv strides must be multiples of 8 elements in [0, 2^31), the head strides >= head_dim");
   MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
   MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
   MI355_CHECK_ARG(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && do_row_stride % 8 == 0 &&
@@ -4396,6 +4446,7 @@ int HSTU_FN(mi355_hstu_attn_bwd_kv)(const void* dout, const void* q, const void*
   a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
   g.dout = (const uint16_t*)dout; g.do_row = do_row_stride; g.do_head = do_head_stride;
   g.dq = (uint16_t*)dq; g.dk = (uint16_t*)dk; g.dv = (uint16_t*)dv;
+  g.dq_row = (int)gs.s[0]; g.dq_head = (int)gs.s[1]; g.dk_row = (int)gs.s[2]; g.dk_head = (int)gs.s[3]; g.dv_row = (int)gs.s[4]; g.dv_head = (int)gs.s[5];
   g.ng = (int)((max_seqlen_k + 31) / 32);
   g.drab = (uint16_t*)drab; g.drab_b = drab_batch_stride; g.drab_h = drab_head_stride; g.drab_r = drab_row_stride;
   const int B = (int)batch, mq = (int)max_seqlen_q, mk = (int)max_seqlen_k;
@@ -4454,6 +4505,7 @@ int HSTU_FN(mi355_hstu_attn_bwd_func)(const void* dout, const void* q, const voi
                              int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
                              void* func_workspace, int64_t func_workspace_bytes, void* workspace, int64_t workspace_bytes,
                              hipStream_t stream) {
+  GradStridesDrop drop_unreached_binding;
   MI355_CHECK_ARG(func != nullptr && n_func >= 1 && (n_func & 1) == 1 && func_bound_stride > 0 && func_neg < 0.f,
                   "func must be int32 [heads or 1][n_func odd][tokens], func_neg negative");
   int causal = 0;

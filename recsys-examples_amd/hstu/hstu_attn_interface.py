@@ -37,6 +37,7 @@ N.register_signatures({
     "mi355_hstu_attn_bwd_ds_bytes": [c_i64, c_i64, c_i64, c_i64],
     "mi355_hstu_attn_bwd_ds_bytes_capped": [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int],
     "mi355_hstu_attn_bwd_hint_tokens": [c_i64],
+    "mi355_hstu_attn_bwd_bind_grad_strides": [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64],
     "mi355_hstu_attn_fwd_hint_tokens": [c_i64],
     "mi355_hstu_attn_fwd_rab": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
                                 c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64, c_p],
@@ -67,6 +68,7 @@ N.register_signatures({
                              c_i64, c_i64, c_p],
 }, {"mi355_hstu_attn_bwd_workspace_bytes": c_i64, "mi355_hstu_attn_bwd_ds_bytes": c_i64,
     "mi355_hstu_attn_bwd_ds_bytes_capped": c_i64, "mi355_hstu_attn_bwd_hint_tokens": None,
+    "mi355_hstu_attn_bwd_bind_grad_strides": None,
     "mi355_hstu_attn_fwd_hint_tokens": None, "mi355_hstu_attn_fwd_hint_tokens_f16": None})
 # the fp16-operand twins of the type-specific entry points (same argument lists)
 _TYPED = ("mi355_hstu_attn_bwd_kv", "mi355_hstu_attn_fwd_hint_tokens", "mi355_hstu_attn_fwd", "mi355_hstu_attn_fwd_kv", "mi355_hstu_attn_fwd_kv_window", "mi355_hstu_attn_fwd_kv_rab", "mi355_hstu_attn_bwd", "mi355_hstu_attn_fwd_window",
@@ -214,22 +216,65 @@ def _bwd_exchange_workspace(q, B, H, D, max_seqlen, plain_causal):
     return ws
 
 
+class _GradOut:
+    """Where a raw backward writes dq / dk / dv (its keyword-only `dq`, `dk`, `dv`: the reference's callers hand the kernel views
+    into one buffer -- the fused layer's duvqk split, fused_hstu_op.py:932-1006; dqkv[:, i], hstu_attn_interface.py:378-388).
+    A given tensor the kernels can address -- q's device and dtype, the gradient's shape, a contiguous last dimension, row and
+    head strides that are multiples of 8 elements, head stride >= head_dim -- is written in place; any other given tensor gets
+    a contiguous stand-in that is copied into it afterwards; None is allocated.  `bind()` hands the strides to the library for
+    the NEXT backward of this thread: call it last, directly in front of that call (nothing that can raise in between)."""
+
+    def __init__(self, q, k, dq, dk, dv):
+        H, D = q.shape[1], q.shape[2]
+        self.given = (dq, dk, dv)
+        if dq is None and dk is None and dv is None:   # (the ordinary call: nothing to look at, its host time is what it was)
+            dq = torch.empty((q.shape[0], H, D), dtype=q.dtype, device=q.device)
+            dk = torch.empty((k.shape[0], H, D), dtype=q.dtype, device=q.device)
+            self.to, self.given, self.plain = [dq, dk, torch.empty_like(dk)], None, True
+            return
+        self.to = []
+        for t, rows in zip(self.given, (q.shape[0], k.shape[0], k.shape[0])):
+            ok = (t is not None and t.device == q.device and t.dtype == q.dtype and tuple(t.shape) == (rows, H, D)
+                  and t.stride(2) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(1) >= D)
+            self.to.append(t if ok else torch.empty((rows, H, D), dtype=q.dtype, device=q.device))
+        self.strides = [s for t in self.to for s in (t.stride(0), t.stride(1))]
+        self.plain = self.strides == [H * D, D] * 3
+
+    def bind(self):
+        if not self.plain:   # (the contiguous layout is what the library assumes unbound)
+            lib().mi355_hstu_attn_bwd_bind_grad_strides(*self.strides)
+
+    def result(self):
+        """(dq, dk, dv) for the caller: the given tensors, filled, where there were any"""
+        if self.given is None:
+            return tuple(self.to)
+        for t, w in zip(self.given, self.to):
+            if t is not None and t is not w:
+                t.copy_(w)
+        return tuple(w if t is None else t for t, w in zip(self.given, self.to))
+
+
 def hstu_varlen_bwd(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, num_contexts, num_targets, target_group_size,
-                    causal, alpha):
-    """Raw backward (stands in for hstu_varlen_bwd_80 / varlen_bwd): returns (dq, dk, dv)."""
+                    causal, alpha, *, dq=None, dk=None, dv=None):
+    """Raw backward (stands in for hstu_varlen_bwd_80 / varlen_bwd): returns (dq, dk, dv); given ones are written in place (_GradOut)."""
     T, H, D = q.shape
     dout = dout.contiguous() if dout.stride(-1) != 1 else dout
-    dq = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
-    dk = torch.empty_like(dq)
-    dv = torch.empty_like(dq)
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
     B = cu_seqlens.numel() - 1
     ws = _bwd_exchange_workspace(q, B, H, D, max_seqlen, bool(causal) and num_contexts is None)
+    go.bind()
     check(_fn("mi355_hstu_attn_bwd", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
                                     v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
                                     ptr(cu_seqlens), B, H, D, int(max_seqlen), ptr(num_contexts), ptr(num_targets),
                                     int(target_group_size), int(causal), c_f(alpha), c_f(float(scaling_seqlen)), ptr(ws),
                                     ws.numel(), stream()), "hstu_attn_bwd")
-    return dq, dk, dv
+    return go.result()
+
+
+def _into(ctx):
+    """dq / dk / dv keywords of the raw backward: the views HstuAttnQKVPackedFunc.backward left on the context, else none"""
+    return dict(zip(("dq", "dk", "dv"), getattr(ctx, "grad_views", (None, None, None))))
 
 
 class HstuAttnVarlenFunc(torch.autograd.Function):
@@ -246,7 +291,7 @@ class HstuAttnVarlenFunc(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, cu, nc, nt = ctx.saved_tensors
         max_seqlen, scaling, g, causal, alpha = ctx.meta
-        dq, dk, dv = hstu_varlen_bwd(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, causal, alpha)
+        dq, dk, dv = hstu_varlen_bwd(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, causal, alpha, **_into(ctx))
         return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
@@ -263,20 +308,21 @@ def hstu_varlen_fwd_window(q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, wl, 
     return out
 
 
-def hstu_varlen_bwd_window(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, wl, wr, alpha):
+def hstu_varlen_bwd_window(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, wl, wr, alpha, *, dq=None, dk=None, dv=None):
     """Raw backward with a local window: returns (dq, dk, dv); same optional dS / P exchange as hstu_varlen_bwd."""
     T, H, D = q.shape
     dout = dout.contiguous() if dout.stride(-1) != 1 else dout
-    dq = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
-    dk, dv = torch.empty_like(dq), torch.empty_like(dq)
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
     B = cu_seqlens.numel() - 1
     ws = _bwd_exchange_workspace(q, B, H, D, max_seqlen, False)
+    go.bind()
     check(_fn("mi355_hstu_attn_bwd_window", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0),
                                            k.stride(0), v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1),
                                            dout.stride(1), ptr(cu_seqlens), B, H, D, int(max_seqlen), int(wl), int(wr),
                                            c_f(alpha), c_f(float(scaling_seqlen)), ptr(ws), ws.numel(), stream()),
           "hstu_attn_bwd_window")
-    return dq, dk, dv
+    return go.result()
 
 
 class HstuAttnWindowFunc(torch.autograd.Function):
@@ -293,7 +339,7 @@ class HstuAttnWindowFunc(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, cu = ctx.saved_tensors
         max_seqlen, scaling, wl, wr, alpha = ctx.meta
-        dq, dk, dv = hstu_varlen_bwd_window(dout, q, k, v, cu, max_seqlen, scaling, wl, wr, alpha)
+        dq, dk, dv = hstu_varlen_bwd_window(dout, q, k, v, cu, max_seqlen, scaling, wl, wr, alpha, **_into(ctx))
         return dq, dk, dv, None, None, None, None, None, None
 
 
@@ -350,19 +396,20 @@ def hstu_varlen_fwd_rab(q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, num_con
 
 
 def hstu_varlen_bwd_rab(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, num_contexts, num_targets, target_group_size,
-                        wl, wr, alpha, rab, has_drab):
+                        wl, wr, alpha, rab, has_drab, *, dq=None, dk=None, dv=None):
     """Raw backward with a relative attention bias: (dq, dk, dv, drab or None).  drab has the shape of rab
     (hstu_api.cpp:659-667, zero outside the sequences / the mask); with one shared bias head it is the sum over the heads,
     formed in fp32 from per-head matrices (the reference adds bf16 pairs atomically: same value, no fixed order)."""
     T, H, D = q.shape
     dout = dout.contiguous() if dout.stride(-1) != 1 else dout
-    dq = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
-    dk, dv = torch.empty_like(dq), torch.empty_like(dq)
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
     B = cu_seqlens.numel() - 1
     N = rab.shape[-1]
     rb, rh, rr = _rab_strides(rab, H)
     drab = torch.zeros((B, H, N, N), dtype=q.dtype, device=q.device) if has_drab else None
     ds = (drab.stride(0), drab.stride(1), drab.stride(2)) if has_drab else (0, 0, 0)
+    go.bind()
     check(_fn("mi355_hstu_attn_bwd_rab", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
                                         v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
                                         ptr(cu_seqlens), B, H, D, int(max_seqlen), ptr(num_contexts), ptr(num_targets),
@@ -370,11 +417,11 @@ def hstu_varlen_bwd_rab(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, n
                                         ptr(rab), rb, rh, rr, ptr(drab), ds[0], ds[1], ds[2], stream()), "hstu_attn_bwd_rab")
     if has_drab and rab.shape[1] == 1 and H > 1:
         drab = drab.float().sum(1, keepdim=True).to(q.dtype)
-    return dq, dk, dv, drab
+    return (*go.result(), drab)
 
 
 def hstu_varlen_bwd_kv(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scaling_seqlen, num_contexts,
-                       num_targets, target_group_size, wl, wr, alpha, rab=None, has_drab=False):
+                       num_targets, target_group_size, wl, wr, alpha, rab=None, has_drab=False, *, dq=None, dk=None, dv=None):
     """Raw backward of a cache-less delta-q call (mi355_hstu_attn_bwd_kv): the queries of a sequence are the last Lq of its Lk
     keys, masks and bias at the absolute positions Lk - Lq + r.  (wl, wr) as window_size: (-1, 0) causal, (-1, -1) full, else a
     local window.  Returns (dq [total_q, H, d], dk, dv [total_k, H, d], drab or None); drab has the shape of rab, summed over the
@@ -383,14 +430,14 @@ def hstu_varlen_bwd_kv(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, 
     if has_drab and rab is None:
         raise ValueError("has_drab needs rab")
     dout = dout.contiguous() if dout.stride(-1) != 1 else dout
-    dq = torch.empty((q.shape[0], H, D), dtype=q.dtype, device=q.device)
-    dk = torch.empty((k.shape[0], H, D), dtype=q.dtype, device=q.device)
-    dv = torch.empty_like(dk)
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
     B = cu_seqlens_q.numel() - 1
     rb, rh, rr = _rab_strides(rab, H) if rab is not None else (0, 0, 0)
     N = int(max_seqlen_k)
     drab = torch.zeros((B, H, N, N), dtype=q.dtype, device=q.device) if has_drab else None
     ds = (drab.stride(0), drab.stride(1), drab.stride(2)) if has_drab else (0, 0, 0)
+    go.bind()
     check(_fn("mi355_hstu_attn_bwd_kv", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
                                            v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
                                            ptr(cu_seqlens_q), ptr(cu_seqlens_k), B, H, D, int(max_seqlen_q), N, ptr(num_contexts),
@@ -399,7 +446,7 @@ def hstu_varlen_bwd_kv(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, 
                                            stream()), "hstu_attn_bwd_kv")
     if has_drab and rab.shape[1] == 1 and H > 1:
         drab = drab.float().sum(1, keepdim=True).to(q.dtype)
-    return dq, dk, dv, drab
+    return (*go.result(), drab)
 
 
 class HstuAttnDeltaQFunc(torch.autograd.Function):
@@ -474,12 +521,12 @@ def hstu_varlen_fwd_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
 
 
 def hstu_varlen_bwd_func(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, num_contexts, num_targets, target_group_size, wl, wr,
-                         alpha, func):
+                         alpha, func, *, dq=None, dk=None, dv=None):
     """Raw backward with arbitrary mask functions read inside the kernels: (dq, dk, dv)"""
     T, H, D = q.shape
     dout = dout.contiguous() if dout.stride(-1) != 1 else dout
-    dq = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
-    dk, dv = torch.empty_like(dq), torch.empty_like(dq)
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
     B = cu_seqlens.numel() - 1
     # tile skipping (round 6): room for the key-block table the backward fills in front of its passes -- which query rows reach
     # every 128-key block, derived from the extents of the functions (72 bytes per key block and function set: the block's query range + the extents of its four 32-row groups; MI355_HSTU_WSKIP=0, the
@@ -487,6 +534,7 @@ def hstu_varlen_bwd_func(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, 
     fws = torch.empty((func.shape[0] if func.shape[0] > 1 else 1) * (T // 128 + B + 1) * 18, dtype=torch.int32, device=q.device)
     # functions of up to two bands take the P / dS exchange backward at head dim 256 (the scratch of hstu_varlen_bwd)
     ws = _bwd_exchange_workspace(q, B, H, D, max_seqlen, False) if (D == 256 and func.shape[1] <= 5) else None
+    go.bind()
     check(_fn("mi355_hstu_attn_bwd_func", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
                                              v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
                                              ptr(cu_seqlens), B, H, D, int(max_seqlen), ptr(num_contexts), ptr(num_targets),
@@ -494,7 +542,7 @@ def hstu_varlen_bwd_func(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, 
                                              ptr(func), func.stride(0) if func.shape[0] > 1 else 0, func.stride(1), func.shape[1],
                                              c_f(_func_neg_value(q.dtype)), ptr(fws), fws.numel() * 4 if fws is not None else 0,
                                              ptr(ws), ws.numel() if ws is not None else 0, stream()), "hstu_attn_bwd_func")
-    return dq, dk, dv
+    return go.result()
 
 
 class HstuAttnFuncFunc(torch.autograd.Function):
@@ -513,7 +561,7 @@ class HstuAttnFuncFunc(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, func, cu, nc, nt = ctx.saved_tensors
         max_seqlen, scaling, g, wl, wr, alpha = ctx.meta
-        dq, dk, dv = hstu_varlen_bwd_func(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, wl, wr, alpha, func)
+        dq, dk, dv = hstu_varlen_bwd_func(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, wl, wr, alpha, func, **_into(ctx))
         return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
 
 
@@ -533,8 +581,67 @@ class HstuAttnRabFunc(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, rab, cu, nc, nt = ctx.saved_tensors
         max_seqlen, scaling, g, wl, wr, alpha, has_drab = ctx.meta
-        dq, dk, dv, drab = hstu_varlen_bwd_rab(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, wl, wr, alpha, rab, has_drab)
+        dq, dk, dv, drab = hstu_varlen_bwd_rab(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, wl, wr, alpha, rab, has_drab, **_into(ctx))
         return dq, dk, dv, drab, None, None, None, None, None, None, None, None, None, None
+
+
+class HstuAttnQKVPackedFunc(torch.autograd.Function):
+    """Self attention over one packed (total, 3, nheads, head_dim) tensor (HstuAttnQKVPackedFunc of the reference,
+    hstu_attn_interface.py:282-429).  `inner` is the autograd function of the call's mask combination (the one
+    hstu_attn_varlen_func would apply: _self_attention picks it), `args` what follows q, k, v in its forward.  The forward runs on
+    the three views of qkv -- no copy, the kernels take strides --; the backward allocates one dqkv and has the raw backward
+    write dqkv[:, 0 / 1 / 2] in place (the inner backward reads them off the context: _into)."""
+
+    @staticmethod
+    def forward(ctx, qkv, inner, *args):
+        q, k, v = qkv.detach().unbind(1)
+        ctx.inner = inner
+        return inner.forward(ctx, q, k, v, *args)
+
+    @staticmethod
+    def backward(ctx, dout):
+        q = ctx.saved_tensors[0]
+        dqkv = torch.empty((q.shape[0], 3, q.shape[1], q.shape[2]), dtype=q.dtype, device=q.device)
+        ctx.grad_views = dqkv.unbind(1)
+        grads = ctx.inner.backward(ctx, dout)   # (dq, dk, dv, then one per entry of args: drab sits where rab does)
+        return (dqkv, None) + tuple(grads[3:])
+
+
+def _self_attention(inner, qkv, q, k, v, *args):
+    """applies the autograd function of a self-attention mask combination to q, k, v, or to the packed qkv they are views of"""
+    if qkv is not None:
+        return HstuAttnQKVPackedFunc.apply(qkv, inner, *args)
+    return inner.apply(q, k, v, *args)
+
+
+def hstu_attn_qkvpacked_func(qkv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, num_contexts=None, num_targets=None,
+                             target_group_size=1, window_size=(-1, -1), alpha=1.0, rab=None, has_drab=False, func=None,
+                             scaling_seqlen=-1):
+    """out (total, nheads, head_dim) = HSTU self attention over qkv (total, 3, nheads, head_dim), bf16 or fp16: the packed entry
+    point of the reference (hstu_attn_interface.py:432-506; same parameters, defaults and ValueErrors).  The same mask
+    combinations as hstu_attn_varlen_func -- contextual / target rows, local window, rab (has_drab), func, func next to rab --
+    through the same kernels; the gradient of qkv is ONE (total, 3, nheads, head_dim) tensor the backward kernels write in place.
+    q and k share `total`, so the call is self attention: cu_seqlens of different shapes or unequal max_seqlen are refused."""
+    window_size = tuple(window_size)
+    if has_drab and (rab is None):
+        raise ValueError("AssertError: rab is None, but has_drab is True, is not allowed in backward")
+    if num_contexts is not None and window_size != (-1, 0):
+        raise ValueError("AssertError: context is True and causal is not True, this is undefined behavior")
+    if num_targets is not None and window_size != (-1, 0):
+        raise ValueError("AssertError: target is True and causal is not True, this is undefined behavior")
+    if num_targets is None and target_group_size < 1:
+        raise ValueError("AssertError: target_group_size should be greater than 0 when target is True")
+    if max_seqlen_q > max_seqlen_k:
+        raise ValueError("AssertError: seq_len_q >= seq_len_k, this is undefined behavior")
+    if max_seqlen_q != max_seqlen_k or cu_seqlens_q.shape != cu_seqlens_k.shape:
+        raise ValueError("a packed qkv holds as many keys as queries (self attention): cu_seqlens_q / cu_seqlens_k must have one "
+                         "shape and max_seqlen_q must equal max_seqlen_k (use hstu_attn_varlen_func for delta-q calls)")
+    if qkv.dim() != 4 or qkv.shape[1] != 3:
+        raise RuntimeError("qkv must be (total, 3, nheads, head_dim)")
+    q, k, v = qkv.unbind(1)
+    return _attn_dispatch(q, k, v, cu_seqlens_q, cu_seqlens_k, None, None, max_seqlen_q, max_seqlen_k, scaling_seqlen, num_contexts,
+                          num_targets, target_group_size, window_size, alpha, rab, has_drab, None, None, None, None, func, -1,
+                          False, qkv)
 
 
 def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k,
@@ -547,6 +654,16 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
     operands (hstu_fp8.py); the output is fp16.  Its backward is by default the bf16 / fp16 backward at the unquantised inputs
     with dout cast to their dtype (straight-through); fp8_backward=True runs the reference's FP8 backward instead (q / k / v /
     dout quantised in the same mode, hstu_fp8.varlen_bwd).  -1 (the default) and None: no quantisation."""
+    return _attn_dispatch(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k, scaling_seqlen,
+                          num_contexts, num_targets, target_group_size, window_size, alpha, rab, has_drab, kv_cache, page_offsets,
+                          page_ids, last_page_lens, func, quant_mode, fp8_backward, None)
+
+
+def _attn_dispatch(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, max_seqlen_q, max_seqlen_k, scaling_seqlen,
+                   num_contexts, num_targets, target_group_size, window_size, alpha, rab, has_drab, kv_cache, page_offsets,
+                   page_ids, last_page_lens, func, quant_mode, fp8_backward, qkv):
+    """The checks and the mask dispatch of hstu_attn_varlen_func; qkv: the packed tensor q, k, v are views of
+    (hstu_attn_qkvpacked_func: a self-attention call, its gradient one packed tensor), else None."""
     if quant_mode is None:
         quant_mode = -1
     if isinstance(quant_mode, bool) or not isinstance(quant_mode, int) or not -1 <= quant_mode <= 5:
@@ -593,7 +710,7 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
                 return hstu_varlen_fwd_func(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), scaling_seqlen,
                                             num_contexts, num_targets, int(target_group_size), wl, wr, float(alpha), func, kv_cache,
                                             page_offsets, page_ids, last_page_lens)
-            return HstuAttnFuncFunc.apply(q, k, v, func, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
+            return _self_attention(HstuAttnFuncFunc, qkv, q, k, v, func, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
                                           int(target_group_size), wl, wr, float(alpha))
     if func is not None:
         # with a relative bias as well (or MI355_HSTU_FUNC_DENSE=1): a bias of 0 / -1e9 through the biased kernels (func_mask_bias)
@@ -623,7 +740,7 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
                                       window=(wl, wr) if local else None, rab=rab, max_seqlen_k=int(max_seqlen_k))
         if rab.shape[-1] != int(max_seqlen_k):
             raise RuntimeError("rab must be (batch, nheads or 1, max_seqlen_k, max_seqlen_k)")
-        return HstuAttnRabFunc.apply(q, k, v, rab, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
+        return _self_attention(HstuAttnRabFunc, qkv, q, k, v, rab, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
                                      int(target_group_size), wl, wr, float(alpha), bool(has_drab))
     if not (wl == -1 and wr in (-1, 0)):
         if not same:
@@ -633,7 +750,7 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
                                                 scaling_seqlen, None, None, 1, wl, wr, float(alpha), False)
             return hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), scaling_seqlen, None, None, 1,
                                       wr == 0, float(alpha), kv_cache, page_offsets, page_ids, last_page_lens, window=(wl, wr))
-        return HstuAttnWindowFunc.apply(q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, wl, wr, float(alpha))
+        return _self_attention(HstuAttnWindowFunc, qkv, q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, wl, wr, float(alpha))
     if kv_cache is not None or not same:
         # keys longer than the queries and / or history keys in the paged cache (the cache: forward only)
         if _delta_q_autograd(q, k, v, None, kv_cache):
@@ -643,5 +760,5 @@ def hstu_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, sequse
         return hstu_varlen_fwd_kv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), scaling_seqlen, num_contexts,
                                   num_targets, int(target_group_size), causal, float(alpha), kv_cache, page_offsets,
                                   page_ids, last_page_lens)
-    return HstuAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
+    return _self_attention(HstuAttnVarlenFunc, qkv, q, k, v, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
                                     int(target_group_size), causal, float(alpha))

@@ -89,33 +89,31 @@ def _bwd(dout, q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, scaling_
     if has_drab and rab is None:
         raise RuntimeError("rab must exist when using has_drab")   # hstu_api.cpp:660
     drab = None
+    # dq / dk / dv as the fused layer gives them -- views into its duvqk buffer, row stride (2 dl + 2 da) H (fused_hstu_op.py:932-1006)
+    # -- go straight down: the kernels write them in place (hstu_attn_interface._GradOut) and they are what is returned
+    into = {"dq": dq, "dk": dk, "dv": dv}
     if func is not None and rab is None:
         _check_func(func, q)
         g = hstu_varlen_bwd_func(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets, int(target_group_size),
-                                 max(int(wl), -1), max(int(wr), -1), float(alpha), func)
+                                 max(int(wl), -1), max(int(wr), -1), float(alpha), func, **into)
     elif func is not None:
         fb = func_mask_bias(func, cu_q, cu_k, int(max_k), q.dtype)
         *g, drab = hstu_varlen_bwd_rab(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets,
                                        int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha),
-                                       fb if rab is None else (rab + fb).clamp_(min=torch.finfo(q.dtype).min), bool(has_drab))
+                                       fb if rab is None else (rab + fb).clamp_(min=torch.finfo(q.dtype).min), bool(has_drab),
+                                       **into)
         if drab is not None and rab.shape[1] == 1 and drab.shape[1] > 1:   # (a per-head mask over one shared bias head)
             drab = drab.float().sum(1, keepdim=True).to(q.dtype)
     elif rab is not None:
         *g, drab = hstu_varlen_bwd_rab(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets,
                                        int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha), rab,
-                                       bool(has_drab))
+                                       bool(has_drab), **into)
     elif window is not None:
-        g = hstu_varlen_bwd_window(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, window[0], window[1], float(alpha))
+        g = hstu_varlen_bwd_window(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, window[0], window[1], float(alpha), **into)
     else:
         g = hstu_varlen_bwd(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets,
-                            int(target_group_size), causal, float(alpha))   # (deterministic by construction: no atomics)
-    res = []
-    for given, new in zip((dq, dk, dv), g):
-        if given is not None:
-            given.copy_(new)
-            new = given
-        res.append(new)
-    return res[0], res[1], res[2], drab
+                            int(target_group_size), causal, float(alpha), **into)   # (deterministic by construction: no atomics)
+    return g[0], g[1], g[2], drab
 
 
 def _fwd_90(q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, scaling_seqlen, num_contexts, num_targets,
