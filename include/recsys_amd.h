@@ -988,6 +988,61 @@ int mi355_hstu_inference_preprocess(const void* item_values, int64_t item_rows, 
                                     const int64_t* out_offsets, int64_t batch, void* out, int64_t out_rows, int64_t D,
                                     int dtype, hipStream_t stream);
 
+/* ---- HSTU positional encoder (csrc/position_ops.hip) ----
+ * Reference paths below are examples/hstu/ops/triton_ops/triton_position.py, Triton kernels there.  All row strides are in
+ * ELEMENTS (>= D, last dimension contiguous); D is any positive value.  offsets [batch + 1], lengths, high_inds, ind_offsets,
+ * num_targets [batch] and timestamps [rows] are device int64.  A table is fp32 or has the dtype of the rows.  No host sync, no
+ * allocation, capturable; rows outside every sequence [offsets[b], offsets[b + 1]) are neither read nor written. */
+
+/* _add_position_embeddings_kernel (:80-137).  For row n of sequence b, i = n + (ind_offsets ? ind_offsets[b] : 0),
+ * idx = i >= high_inds[b] ? high_inds[b] : i, out = round(jagged * scale + dense[idx]) with one fp32 fused multiply-add.
+ * UNLIKE the reference, idx is then clamped into [0, K - 1]: nothing outside dense [K, D] is ever accessed. */
+int mi355_hstu_add_position_embeddings(const void* jagged, int64_t jagged_stride, int64_t rows, int64_t D, int dtype,
+                                       const int64_t* offsets, const int64_t* high_inds, const int64_t* ind_offsets,
+                                       int64_t batch, const void* dense, int64_t dense_stride, int64_t K, int dense_dtype,
+                                       float scale, void* out, int64_t out_stride, hipStream_t stream);
+
+/* _add_position_embeddings_bwd_kernel (:141-211), the case without ind_offsets (:268-270).  d_jagged = round(d_out * scale) when
+ * d_jagged is non-null (the caller passes null for scale == 1 and returns d_out).  d_dense[k] = the sum of the d_out rows whose
+ * idx is k, accumulated in fp32 in a fixed order (bitwise reproducible, no atomics) and rounded once to dense_dtype (the
+ * reference rounds to the dtype of d_out first); all K rows are written, a row nothing maps to as zeros.  workspace: 32-byte
+ * aligned, mi355_hstu_add_position_embeddings_bwd_workspace_bytes(rows, batch, D) bytes, contents irrelevant. */
+int64_t mi355_hstu_add_position_embeddings_bwd_workspace_bytes(int64_t rows, int64_t batch, int64_t D);
+int mi355_hstu_add_position_embeddings_bwd(const void* d_out, int64_t d_out_stride, int64_t rows, int64_t D, int dtype,
+                                           const int64_t* offsets, const int64_t* high_inds, int64_t batch, float scale,
+                                           void* d_jagged, int64_t d_jagged_stride, void* d_dense, int64_t d_dense_stride,
+                                           int64_t K, int dense_dtype, void* workspace, int64_t workspace_bytes,
+                                           hipStream_t stream);
+
+/* _add_timestamp_position_embeddings_kernel (:309-404).  Row n of sequence b [s, e):
+ *   high = lengths[b] - (num_targets ? (interleave_targets ? 2 : 1) * num_targets[b] : 0);
+ *   p = high - min(n, high) + max_contextual_seq_len; p = min(p, Np - 1); if n < max_contextual_seq_len: p = n;
+ *   dt = max(float(timestamps[e - 1] - timestamps[s + n] + time_delta), 1e-6f) / time_bucket_increments (IEEE division);
+ *   t = int32(f(dt) * time_bucket_scale), f = sqrtf (time_bucket_fn 0, correctly rounded) or logf (1), clamped into
+ *   [0, num_time_buckets];  out = round(seq + round(pos_emb[p] + ts_emb[t])), both sums in fp32 (:399).
+ * UNLIKE the reference, p is clamped into [0, Np - 1] and t into [0, Nt - 1] before the loads.  pos_inds / ts_inds (int32
+ * [rows], may be null) receive p and t of every row. */
+int mi355_hstu_add_timestamp_position_embeddings(const void* seq, int64_t seq_stride, int64_t rows, int64_t D, int dtype,
+                                                 const int64_t* offsets, const int64_t* lengths, int64_t batch,
+                                                 const void* pos_emb, int64_t pos_stride, int64_t Np, const void* ts_emb,
+                                                 int64_t ts_stride, int64_t Nt, int table_dtype, const int64_t* timestamps,
+                                                 const int64_t* num_targets, int interleave_targets,
+                                                 int64_t max_contextual_seq_len, int time_bucket_fn, int64_t num_time_buckets,
+                                                 float time_bucket_increments, float time_bucket_scale, int64_t time_delta,
+                                                 void* out, int64_t out_stride, int32_t* pos_inds, int32_t* ts_inds,
+                                                 hipStream_t stream);
+
+/* _add_embeddings_bwd_kernel (:434-482, float atomics there).  d_table[k] = the sum of d_out[sorted_rows[i]] over the i with
+ * sorted_keys[i] == k: sorted_keys (int32 [count]) ascending, sorted_rows (int64 [count]) the d_out row of each entry (a stable
+ * sort of the forward's pos_inds / ts_inds).  fp32 accumulation in list order per chunk of 64 or 32 entries, chunks in order: bitwise
+ * reproducible, no atomics; all K rows written in table_dtype; keys outside [0, K) and rows outside [0, rows) are skipped.
+ * workspace: 32-byte aligned, mi355_hstu_index_rows_sum_workspace_bytes(count, K, D) bytes. */
+int64_t mi355_hstu_index_rows_sum_workspace_bytes(int64_t count, int64_t K, int64_t D);
+int mi355_hstu_index_rows_sum(const void* d_out, int64_t d_out_stride, int64_t rows, int64_t D, int dtype,
+                              const int32_t* sorted_keys, const int64_t* sorted_rows, int64_t count, void* d_table,
+                              int64_t table_stride, int64_t K, int table_dtype, void* workspace, int64_t workspace_bytes,
+                              hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

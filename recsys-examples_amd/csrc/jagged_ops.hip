@@ -22,6 +22,7 @@
 // No row outside a tensor is touched whatever the offsets hold: a row index outside [0, rows[t]) or [0, total_rows) is
 // skipped.
 #include "common.h"
+#include "jagged_dev.h"
 #include "../../include/recsys_amd.h"
 
 namespace mi355 {
@@ -69,21 +70,6 @@ template <> struct Piece<16> { typedef unsigned int T __attribute__((ext_vector_
 template <> struct Piece<8> { typedef unsigned int T __attribute__((ext_vector_type(2))); };
 template <> struct Piece<4> { typedef unsigned int T; };
 template <> struct Piece<2> { typedef unsigned short T; };
-
-__device__ __forceinline__ uintptr_t shfl_addr(uintptr_t v, int src) {
-  const int lo = __shfl((int)(v & 0xffffffffu), src, 64), hi = __shfl((int)(v >> 32), src, 64);
-  return (uintptr_t)(unsigned)lo | ((uintptr_t)(unsigned)hi << 32);
-}
-
-// largest b in [0, B - 1] with off[b] <= m
-__device__ __forceinline__ int64_t sample_of(const int64_t* off, int64_t B, int64_t m) {
-  int64_t lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= m) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // The wave copies `nrows` rows of `vpr` pieces of W bytes: lane l holds the source and destination address of row l (0: skip it).
 template <int W>
@@ -198,16 +184,6 @@ static inline int access_width(uint64_t row_bytes, uintptr_t align_bits) {
   const uint64_t x = row_bytes | (uint64_t)align_bits;
   return (x & 15) == 0 ? 16 : (x & 7) == 0 ? 8 : (x & 3) == 0 ? 4 : 2;
 }
-
-// Rows per wave: 64 while the call has waves to spare; halved (down to 4) while it would leave the chip short of waves and a
-// wave would still move 4 KiB.
-static inline int rows_per_wave_log2(int64_t rows, uint64_t row_bytes) {
-  int k = 6;
-  while (k > 2 && ceil_div(rows, (int64_t)1 << k) < 4096 && (row_bytes << (k - 1)) >= 4096) --k;
-  return k;
-}
-
-static inline int log2_or_minus1(uint32_t v) { return (v & (v - 1)) == 0 ? __builtin_ctz(v) : -1; }
 
 }  // namespace mi355
 

@@ -11,9 +11,12 @@ reference's schemas, so `commons/ops/cuda_ops/JaggedTensorOpFunction.py`, `examp
   them itself when the examples import it, and a second registration of the same op raises.
 * `jagged_2D_tensor_concat` is the library's own one-call form of the concat: one launch forward, one backward, no workload
   array and no cumulative sum.
+* `split_2D_jagged` (alias `triton_split_2D_jagged`, the name `examples/hstu/modules/hstu_processor.py` imports from the
+  reference's Triton package) is the inverse of the two-tensor concat over the same kernel; it is a Python function, not an
+  eleventh op schema.
 """
 import ctypes
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -373,3 +376,85 @@ def jagged_2D_tensor_concat(values_list: List[torch.Tensor], offsets_list: List[
         else:
             result = _JaggedConcat.apply([_complete_offsets(result[1]), _complete_offsets(part[1])], result[0], part[0])
     return result
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# split of a merged jagged tensor into its two parts: the inverse of the two-tensor concat
+# ---------------------------------------------------------------------------------------------------------------------
+class _Split2DJagged(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, offsets_a, offsets_b, rows_a, rows_b):
+        # (the public function has validated the arguments: int64 contiguous offsets, contiguous 2-D values on the GPU)
+        merged_offsets = offsets_a + offsets_b
+        values_a = values.new_empty((rows_a, values.size(1)))
+        values_b = values.new_empty((rows_b, values.size(1)))
+        if values.size(0) > 0:
+            _concat_launch([values_a, values_b], [offsets_a, offsets_b], merged_offsets, values, 1, checked=True)
+        ctx.save_for_backward(merged_offsets, offsets_a, offsets_b)
+        ctx.rows = values.size(0)
+        return values_a, values_b
+
+    @staticmethod
+    def backward(ctx, grad_a, grad_b):
+        merged_offsets, offsets_a, offsets_b = ctx.saved_tensors
+        d_values = grad_a.new_empty((ctx.rows, grad_a.size(1)))
+        if ctx.rows > 0:
+            _concat_launch([grad_a.contiguous(), grad_b.contiguous()], [offsets_a, offsets_b], merged_offsets, d_values, 0,
+                           checked=True)
+        return d_values, None, None, None, None
+
+
+def split_2D_jagged(values: torch.Tensor, max_seq_len: int, offsets_a: Optional[torch.Tensor] = None,
+                    offsets_b: Optional[torch.Tensor] = None, dense_size: int = 0, n_prefix_to_right: int = 0,
+                    seq_len_a=None, seq_len_b=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cuts every sample of the jagged `values` [rows, D] into its leading part A and its trailing part B (the reference's
+    triton_split_2D_jagged, commons/ops/triton_ops/triton_jagged.py:1330-1349): the inverse of the two-tensor concat, one
+    launch of mi355_jagged_concat forward (direction 1) and one backward (direction 0).  Differentiable in `values`.
+
+    A side whose offsets are None is dense: `dense_size` rows per sample, returned as [B, dense_size, D]; at most one side may
+    be.  With both sides jagged, `seq_len_a` / `seq_len_b` (int or one-element tensor: the row count of each part) spare the
+    host read of the last offset.  `max_seq_len` is part of the reference's signature (its launch grid) and is unused here.
+    `n_prefix_to_right` != 0 (a prefix of A moved behind B) is not implemented; no caller in examples/hstu passes it."""
+    if n_prefix_to_right != 0:
+        raise NotImplementedError("split_2D_jagged: n_prefix_to_right != 0 is not implemented")
+    if values.dim() != 2:
+        raise ValueError(f"values must be 2-D, got {values.dim()}-D")
+    if offsets_a is None and offsets_b is None:
+        raise ValueError("offsets_a and offsets_b cannot both be None")
+    for o in (offsets_a, offsets_b):
+        if o is not None and (o.dim() != 1 or o.numel() < 2):
+            raise ValueError("every offsets tensor must be 1-D with batch + 1 entries, batch >= 1")
+    if offsets_a is not None and offsets_b is not None and offsets_a.numel() != offsets_b.numel():
+        raise ValueError("offsets_a and offsets_b must hold the same number of entries")
+    if (offsets_a is None or offsets_b is None) and dense_size < 0:
+        raise ValueError("dense_size must be >= 0")
+    if not values.is_cuda:
+        raise N.NativeError("split_2D_jagged expects GPU tensors (no CPU fallback exists)")
+    if values.dtype not in _DT:
+        raise N.NativeError(f"unsupported dtype {values.dtype}")
+    given = offsets_b if offsets_a is None else offsets_a
+    if given.device != values.device or (offsets_b is not None and offsets_b.device != values.device):
+        raise ValueError("offsets must be on the device of the values")
+    B, rows = given.numel() - 1, values.size(0)
+    dense_a, dense_b = offsets_a is None, offsets_b is None
+    if dense_a or dense_b:
+        dense_offsets = torch.arange(B + 1, dtype=torch.int64, device=values.device) * dense_size
+        if B * dense_size > rows:
+            raise ValueError(f"values holds {rows} rows, fewer than batch * dense_size = {B * dense_size}")
+    if dense_a:
+        offsets_a, rows_a, rows_b = dense_offsets, B * dense_size, rows - B * dense_size
+    elif dense_b:
+        offsets_b, rows_b, rows_a = dense_offsets, B * dense_size, rows - B * dense_size
+    else:
+        rows_a = int(offsets_a[-1].item() if seq_len_a is None else seq_len_a)
+        rows_b = int(offsets_b[-1].item() if seq_len_b is None else seq_len_b)
+    values = values if values.is_contiguous() else values.contiguous()
+    values_a, values_b = _Split2DJagged.apply(values, _offsets_i64(offsets_a), _offsets_i64(offsets_b), rows_a, rows_b)
+    if dense_a:
+        values_a = values_a.reshape(B, dense_size, values.size(1))
+    if dense_b:
+        values_b = values_b.reshape(B, dense_size, values.size(1))
+    return values_a, values_b
+
+
+triton_split_2D_jagged = split_2D_jagged

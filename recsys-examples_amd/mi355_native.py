@@ -190,6 +190,17 @@ _SIGS = {
     "mi355_jagged_concat": [c_int, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p],
     "mi355_jagged_block_workloads": [c_int, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p],
     "mi355_hstu_inference_preprocess": [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p],
+    "mi355_hstu_add_position_embeddings": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_f,
+                                           c_p, c_i64, c_p],
+    "mi355_hstu_add_position_embeddings_bwd_workspace_bytes": [c_i64, c_i64, c_i64],
+    "mi355_hstu_add_position_embeddings_bwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_i64, c_f, c_p, c_i64, c_p, c_i64,
+                                               c_i64, c_int, c_p, c_i64, c_p],
+    "mi355_hstu_add_timestamp_position_embeddings": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_i64,  # seq, offsets, lengths
+                                                     c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int,  # tables
+                                                     c_p, c_p, c_int, c_i64, c_int, c_i64, c_f, c_f, c_i64,  # index maps
+                                                     c_p, c_i64, c_p, c_p, c_p],
+    "mi355_hstu_index_rows_sum_workspace_bytes": [c_i64, c_i64, c_i64],
+    "mi355_hstu_index_rows_sum": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -217,6 +228,8 @@ _RESTYPES = {
     "mi355_demb_aux_numel": c_i64,
     "mi355_demb_forward_fused_workspace_bytes": c_i64,
     "mi355_hstu_fp8_blocks_bound": c_i64,
+    "mi355_hstu_add_position_embeddings_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_index_rows_sum_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
