@@ -3664,87 +3664,90 @@ __global__ void __launch_bounds__(512) hstu_bwd_kv_pc_kernel(BwdAttnArgs g) {
   if (kj < s.L) store_acc_rows<D>(acc_dk, g.dk + (int64_t)(s.start + kj) * g.dk_row + (int64_t)h * g.dk_head, hi);
 }
 
+// ---- the host layer: launch rules per head dim, the call record the entry points fill, the entry points themselves
+
+// MI355_HSTU_FWD (a TEST hook, read once): 0 / unset = the rules of launch_fwd_pc; 1 = 64-row waves at every length, 2 = ... in pairs on
+// every batch, 3 = 32-row waves at every length, 4 = ... in pairs on every batch, 5 = the one-kind register-staged kernel (launch_fwd)
+static int fwd_hook() {
+  static const int v = getenv("MI355_HSTU_FWD") ? atoi(getenv("MI355_HSTU_FWD")) : 0;
+  return v;
+}
+
+// Launches kernel instance K with `smem` bytes of dynamic LDS (an instance always asks for the same size); its first launch in
+// this process raises the instance's limit to that size.  Nonzero = the attribute could not be set (the error text is set).
+template <auto K, typename Args>
+static int launch(dim3 grid, dim3 block, size_t smem, hipStream_t stream, const Args& args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) { mi355_set_error(hipGetErrorString(e)); return MI355_ELAUNCH; }
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(K, grid, block, smem, stream, args);
+  return MI355_OK;
+}
+// the end of a sequence of launches: `failed` = one of its launch() calls returned nonzero; otherwise what HIP has to report
+static int launched(int failed) {
+  if (failed) return MI355_ELAUNCH;
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
+}
+
 template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
-static void launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
+static int launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;
   const size_t timg = (size_t)BQ * TrStride<D>::value;
   const size_t smem = (size_t)(BQ * (D + 8) + (kDK ? BQ * (D + 8) + timg : 0) + (kDV ? timg : 0)) * sizeof(uint16_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>), grid, dim3(256), smem, stream, g);
+  return launch<hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>>(grid, dim3(256), smem, stream, g);
 }
 template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false>
-static void launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
+static int launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem_q = (size_t)(2 * BK * (D + 8) + BK * TrStride<D>::value) * sizeof(uint16_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>), grid, dim3(256), smem_q, stream, g);
+  return launch<hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>>(grid, dim3(256), smem_q, stream, g);
 }
 
 template <int D>   // (head dim 128; 256 takes launch_bwd_x8)
-static void launch_bwd_v_p(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
+static int launch_bwd_v_p(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem = (size_t)(HSTU_XSTEP * TrStride<D>::value) * sizeof(uint16_t);
-  hipLaunchKernelGGL((hstu_bwd_v_p_kernel<D>), grid, dim3(256), smem, stream, g);
+  return launch<hstu_bwd_v_p_kernel<D>>(grid, dim3(256), smem, stream, g);
 }
 
 template <int D>
-static void launch_bwd_q_ds(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
+static int launch_bwd_q_ds(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem = (size_t)(HSTU_XSTEP * TrStride<D>::value + 4 * (HSTU_XSTEP / 32) * 1024) * sizeof(uint16_t);
-  hipLaunchKernelGGL((hstu_bwd_q_ds_kernel<D>), grid, dim3(256), smem, stream, g);
+  return launch<hstu_bwd_q_ds_kernel<D>>(grid, dim3(256), smem, stream, g);
 }
 
-// the DMA-staged one-GEMM passes (head dim 256): dV and dQ in one launch of 4-wave workgroups, two per CU (hstu_bwd_vq8_kernel)
-template <bool kFunc = false>
-static void launch_bwd_x8(const BwdAttnArgs& g, int B, int max_seqlen, hipStream_t stream) {
+// the S-wave / K-wave dK pass of head dim 256 (it writes P and dS), then the DMA-staged one-GEMM passes: dV and dQ in one launch of
+// 4-wave workgroups, two per CU (hstu_bwd_vq8_kernel)
+template <bool kFunc>
+static int launch_bwd_pc_x8(const BwdAttnArgs& g, dim3 grid, int B, int max_seqlen, hipStream_t stream) {
+  const size_t smem_pc = (size_t)(6 * 32 * 256 + 2 * 4 * 2 * 64 * 8) * sizeof(uint16_t) + (kFunc ? 2 * 192 * sizeof(int) : 0);
   const size_t smem = (size_t)(2 * 64 * 256 + kNW8 * 2 * 1024) * sizeof(uint16_t);   // two dO / K tiles + the dS patches
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_vq8_kernel<256, kFunc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
   const int nblk = (max_seqlen + 32 * kNW8 - 1) / (32 * kNW8);
-  hipLaunchKernelGGL((hstu_bwd_vq8_kernel<256, kFunc>), dim3(g.f.H, B, 2 * nblk), dim3(64 * kNW8), smem, stream, g);
+  return launched(launch<hstu_bwd_kv_pc_kernel<256, kFunc>>(grid, dim3(512), smem_pc, stream, g) ||
+                  launch<hstu_bwd_vq8_kernel<256, kFunc>>(dim3(g.f.H, B, 2 * nblk), dim3(64 * kNW8), smem, stream, g));
 }
 
 template <int D>
 static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) {
   dim3 grid(g.f.H, B, (max_seqlen + kBM - 1) / kBM);   // block rank slowest: see launch_fwd
-  // (round 6) mask functions of up to two bands take the exchange backward at head dim 256 when the caller brought the scratch
-  const bool func_x = D == 256 && g.f.func && !g.f.rab && g.f.n_func <= 5 && g.p_ws && g.ds_ws;
   if constexpr (D == 256) {
-    if (func_x) {
+    // (round 6) mask functions of up to two bands take the exchange backward at head dim 256 when the caller brought the scratch
+    if (g.f.func && !g.f.rab && g.f.n_func <= 5 && g.p_ws && g.ds_ws) {
       g.bq_kv = 32;
-      const size_t smem_pc = (size_t)(6 * 32 * 256 + 2 * 4 * 2 * 64 * 8) * sizeof(uint16_t) + 2 * 192 * sizeof(int);
-      static bool attr_pcf = false;
-      if (!attr_pcf) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_pc_kernel<256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_pc);
-        attr_pcf = true;
-      }
-      hipLaunchKernelGGL((hstu_bwd_kv_pc_kernel<256, true>), grid, dim3(512), smem_pc, stream, g);
-      launch_bwd_x8<true>(g, B, max_seqlen, stream);
-      MI355_LAUNCH_CHECK();
-      return MI355_OK;
+      return launch_bwd_pc_x8<true>(g, grid, B, max_seqlen, stream);
     }
   }
   if (g.f.rab || g.f.func) {   // attention bias / mask functions: the recomputing passes (S needs the bias in every pass), dS doubles as d rab
     g.ds_ws = g.p_ws = nullptr;
     g.bq_kv = 64;
-    if constexpr (D >= 128) {
-      launch_bwd_kv<D, 64, 1, false, false, true>(g, grid, stream);
-      launch_bwd_kv<D, 32, 2, false, false, true>(g, grid, stream);
-      launch_bwd_q<D, D >= 256 ? 32 : 64, false, true>(g, grid, stream);
-    } else {
-      launch_bwd_kv<D, 64, 0, false, false, true>(g, grid, stream);
-      launch_bwd_q<D, 64, false, true>(g, grid, stream);
-    }
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    if constexpr (D >= 128)
+      return launched(launch_bwd_kv<D, 64, 1, false, false, true>(g, grid, stream) ||
+                      launch_bwd_kv<D, 32, 2, false, false, true>(g, grid, stream) ||
+                      launch_bwd_q<D, D >= 256 ? 32 : 64, false, true>(g, grid, stream));
+    else
+      return launched(launch_bwd_kv<D, 64, 0, false, false, true>(g, grid, stream) || launch_bwd_q<D, 64, false, true>(g, grid, stream));
   }
   if constexpr (D >= 256) {
     if (g.p_ws) {          // dK pass first (it writes P and dS), then the two one-GEMM passes
@@ -3752,44 +3755,24 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
       // 64-row steps (no registers left to prefetch the next step's Q / dO rows: 0.153 against 0.149 ms at C3, 1.33 against 1.29 ms
       // at L = 4096), and the register-staged one-GEMM passes instead of the DMA-staged ones
       g.bq_kv = 32;
-      const size_t smem_pc = (size_t)(6 * 32 * 256 + 2 * 4 * 2 * 64 * 8) * sizeof(uint16_t);
-      static bool attr_pc = false;
-      if (!attr_pc) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_bwd_kv_pc_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_pc);
-        attr_pc = true;
-      }
-      hipLaunchKernelGGL((hstu_bwd_kv_pc_kernel<256>), grid, dim3(512), smem_pc, stream, g);
-      launch_bwd_x8(g, B, max_seqlen, stream);
-      MI355_LAUNCH_CHECK();
-      return MI355_OK;
+      return launch_bwd_pc_x8<false>(g, grid, B, max_seqlen, stream);
     }
     g.bq_kv = 64;
-    launch_bwd_kv<D, 64, 1, true>(g, grid, stream);
-    launch_bwd_kv<D, 64, 2, false>(g, grid, stream);
-    if (g.ds_ws) launch_bwd_q_ds<D>(g, grid, stream);
-    else launch_bwd_q<D, 32, true>(g, grid, stream);
+    return launched(launch_bwd_kv<D, 64, 1, true>(g, grid, stream) || launch_bwd_kv<D, 64, 2, false>(g, grid, stream) ||
+                    (g.ds_ws ? launch_bwd_q_ds<D>(g, grid, stream) : launch_bwd_q<D, 32, true>(g, grid, stream)));
   } else if constexpr (D >= 128) {
     g.bq_kv = 32;
-    if (g.p_ws) {
-      launch_bwd_kv<D, 32, 2, false, true>(g, grid, stream);
-      launch_bwd_v_p<D>(g, grid, stream);
-      launch_bwd_q_ds<D>(g, grid, stream);
-      MI355_LAUNCH_CHECK();
-      return MI355_OK;
-    }
-    launch_bwd_kv<D, 64, 1, false>(g, grid, stream);
-    launch_bwd_kv<D, 32, 2, false>(g, grid, stream);
-    if (g.ds_ws) launch_bwd_q_ds<D>(g, grid, stream);
-    else launch_bwd_q<D, 64, false>(g, grid, stream);
+    if (g.p_ws)
+      return launched(launch_bwd_kv<D, 32, 2, false, true>(g, grid, stream) || launch_bwd_v_p<D>(g, grid, stream) ||
+                      launch_bwd_q_ds<D>(g, grid, stream));
+    return launched(launch_bwd_kv<D, 64, 1, false>(g, grid, stream) || launch_bwd_kv<D, 32, 2, false>(g, grid, stream) ||
+                    (g.ds_ws ? launch_bwd_q_ds<D>(g, grid, stream) : launch_bwd_q<D, 64, false>(g, grid, stream)));
   } else {
     g.bq_kv = 64;
     g.p_ws = nullptr;          // (dV and dK come out of ONE pass at these head dims: only dS is handed on)
-    launch_bwd_kv<D, 64, 0, false>(g, grid, stream);
-    if (g.ds_ws) launch_bwd_q_ds<D>(g, grid, stream);
-    else launch_bwd_q<D, 64, false>(g, grid, stream);
+    return launched(launch_bwd_kv<D, 64, 0, false>(g, grid, stream) ||
+                    (g.ds_ws ? launch_bwd_q_ds<D>(g, grid, stream) : launch_bwd_q<D, 64, false>(g, grid, stream)));
   }
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
 }
 
 // Delta-q backward (mi355_hstu_attn_bwd_kv): the recomputing passes with kDq -- the dV / dK pass(es) over grids of key blocks, the
@@ -3800,119 +3783,64 @@ static int launch_bwd_dq(BwdAttnArgs g, int B, int max_q, int max_k, hipStream_t
   g.ds_ws = g.p_ws = nullptr;
   g.bq_kv = 64;
   constexpr bool kPre = D >= 256 && !kRab;   // (as launch_bwd: only the unbiased 256 passes prefetch)
-  if constexpr (D >= 128) {
-    launch_bwd_kv<D, 64, 1, kPre, false, kRab, true>(g, gk, stream);
-    launch_bwd_kv<D, (D >= 256 && !kRab) ? 64 : 32, 2, false, false, kRab, true>(g, gk, stream);
-  } else {
-    launch_bwd_kv<D, 64, 0, false, false, kRab, true>(g, gk, stream);
-  }
-  if (max_q > 0) launch_bwd_q<D, D >= 256 ? 32 : 64, kPre, kRab, true>(g, gq, stream);   // (no queries at all: dK = dV = 0 is the whole result)
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  int failed;
+  if constexpr (D >= 128)
+    failed = launch_bwd_kv<D, 64, 1, kPre, false, kRab, true>(g, gk, stream) ||
+             launch_bwd_kv<D, (D >= 256 && !kRab) ? 64 : 32, 2, false, false, kRab, true>(g, gk, stream);
+  else
+    failed = launch_bwd_kv<D, 64, 0, false, false, kRab, true>(g, gk, stream);
+  // (no queries at all: dK = dV = 0 is the whole result)
+  return launched(failed || (max_q > 0 && launch_bwd_q<D, D >= 256 ? 32 : 64, kPre, kRab, true>(g, gq, stream)));
 }
 
-// the two-waves-per-SIMD forward (head dim 256; MI355_HSTU_FWD = 5: the one-kind register-staged kernel, see mi355_hstu_attn_fwd_kv)
+// the two-waves-per-SIMD forward (head dim 256): S waves + O waves
 template <int D>
 static int launch_fwd_pc(const AttnArgs& a, int B, int max_seqlen, hipStream_t stream, bool dense_batch) {
   const size_t smem = (size_t)(4 * kBN * D + 2 * 4 * 4 * 64 * 8) * sizeof(uint16_t);   // K ring + V ring + P ring = 160 KB
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_pair_kernel<D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return MI355_ELAUNCH;
-    attr_set = true;
-  }
-  // MI355_HSTU_FWD (a TEST hook, read once): 0 / unset = the rules below; 1 = 64-row waves at every length, 2 = ... in pairs on every
-  // batch, 3 = 32-row waves at every length, 4 = ... in pairs on every batch (5 = the one-kind kernel: see mi355_hstu_attn_fwd_kv)
-  static const int fwd_hook = getenv("MI355_HSTU_FWD") ? atoi(getenv("MI355_HSTU_FWD")) : 0;
+  const int hook = fwd_hook();
   // row blocks in (heavy, light) pairs per workgroup: dense batches only (every sequence max_seqlen rows: the caller said so with
   // mi355_hstu_attn_fwd_hint_tokens).  On a jagged batch the pairs of a long column are as heavy as before but half as many
   // workgroups share the machine and the tail grows (C4 shape 340 -> 355 us).
-  const bool paired = fwd_hook == 2 || fwd_hook == 4 || dense_batch;
+  const bool paired = hook == 2 || hook == 4 || dense_batch;
   // 64 query rows per wave (two MFMAs per LDS fragment) from 1 025 rows: +4-6 % at L >= 2048, +1-4 % on jagged Zipf-to-4096 batches,
   // level at 768-1024, -2 % at C3 and -6 % at L = 256 (fewer, larger units per short column)
-  const bool q2 = fwd_hook == 1 || fwd_hook == 2 || (fwd_hook != 3 && fwd_hook != 4 && max_seqlen > 1024) || a.func;
+  const bool q2 = hook == 1 || hook == 2 || (hook != 3 && hook != 4 && max_seqlen > 1024) || a.func;
   const int nblk = (max_seqlen + kBM - 1) / kBM;
   const bool win = a.wl >= 0 || a.wr >= 0;
-  const dim3 grid(a.H, B, paired ? (nblk + 1) / 2 : nblk);
+  const dim3 grid(a.H, B, paired ? (nblk + 1) / 2 : nblk), block(512);
   if (q2) {
-    static bool attr_q2 = false;
-    if (!attr_q2) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return MI355_ELAUNCH;
-      attr_q2 = true;
-    }
-    if (a.func) {     // mask functions: the window-capable variants + the functions
-      static bool attr_fn = false;
-      if (!attr_fn) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_q2_kernel<D, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-          return MI355_ELAUNCH;
-        attr_fn = true;
-      }
-      if (paired) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, true, true>), grid, dim3(512), smem, stream, a);
-      else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, false, true>), grid, dim3(512), smem, stream, a);
-    } else if (paired) {
-      if (win) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, true>), grid, dim3(512), smem, stream, a);
-      else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, false, true>), grid, dim3(512), smem, stream, a);
-    } else {
-      if (win) hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, true, false>), grid, dim3(512), smem, stream, a);
-      else hipLaunchKernelGGL((hstu_fwd_q2_kernel<D, false, false>), grid, dim3(512), smem, stream, a);
-    }
-  } else if (paired) {
-    if (win) hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, true, true>), grid, dim3(512), smem, stream, a);
-    else hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, false, true>), grid, dim3(512), smem, stream, a);
-  } else {
-    if (win) hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, true, false>), grid, dim3(512), smem, stream, a);
-    else hipLaunchKernelGGL((hstu_fwd_pair_kernel<D, false, false>), grid, dim3(512), smem, stream, a);
+    if (a.func)      // mask functions: the window-capable variants + the functions
+      return launched(paired ? launch<hstu_fwd_q2_kernel<D, true, true, true>>(grid, block, smem, stream, a)
+                             : launch<hstu_fwd_q2_kernel<D, true, false, true>>(grid, block, smem, stream, a));
+    if (paired)
+      return launched(win ? launch<hstu_fwd_q2_kernel<D, true, true>>(grid, block, smem, stream, a)
+                          : launch<hstu_fwd_q2_kernel<D, false, true>>(grid, block, smem, stream, a));
+    return launched(win ? launch<hstu_fwd_q2_kernel<D, true, false>>(grid, block, smem, stream, a)
+                        : launch<hstu_fwd_q2_kernel<D, false, false>>(grid, block, smem, stream, a));
   }
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  if (paired)
+    return launched(win ? launch<hstu_fwd_pair_kernel<D, true, true>>(grid, block, smem, stream, a)
+                        : launch<hstu_fwd_pair_kernel<D, false, true>>(grid, block, smem, stream, a));
+  return launched(win ? launch<hstu_fwd_pair_kernel<D, true, false>>(grid, block, smem, stream, a)
+                      : launch<hstu_fwd_pair_kernel<D, false, false>>(grid, block, smem, stream, a));
 }
 
 template <int D>
 static int launch_fwd(const AttnArgs& a, int B, int max_seqlen, hipStream_t stream) {
   const size_t smem = (size_t)(kBN * (D + 8) + D * (kBN + 8)) * sizeof(uint16_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_kernel<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(hstu_fwd_kernel<D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess) return MI355_ELAUNCH;
-    attr_set = true;
-  }
   // Dispatch order is x, then y, then z: with the block rank in z, ALL sequences' heaviest (causal: latest) row blocks
   // are handed out first and the light ones fill in behind them.  With the rank in x (per-sequence order 8,6,4,2 key
   // tiles at L = 512) the CUs freed first drew heavy blocks again and the slowest CU did 16 tiles where 10 is the mean.
   dim3 grid(a.H, B, (max_seqlen + kBM - 1) / kBM);
-  if (a.rab || a.func) hipLaunchKernelGGL((hstu_fwd_kernel<D, true, true>), grid, dim3(256), smem, stream, a);
-  else if (a.wl >= 0 || a.wr >= 0) hipLaunchKernelGGL((hstu_fwd_kernel<D, true>), grid, dim3(256), smem, stream, a);
-  else hipLaunchKernelGGL((hstu_fwd_kernel<D, false>), grid, dim3(256), smem, stream, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  if (a.rab || a.func) return launched(launch<hstu_fwd_kernel<D, true, true>>(grid, dim3(256), smem, stream, a));
+  if (a.wl >= 0 || a.wr >= 0) return launched(launch<hstu_fwd_kernel<D, true>>(grid, dim3(256), smem, stream, a));
+  return launched(launch<hstu_fwd_kernel<D, false>>(grid, dim3(256), smem, stream, a));
 }
 
 HSTU_NS_END
 
 using namespace mi355;
 
-// local window of the call in flight on this thread (set by the *_window entry points around the plain ones)
-static thread_local int tl_wl = -1, tl_wr = -1;
-// rows of q of the NEXT forward call on this thread (mi355_hstu_attn_fwd_hint_tokens; 0 = unknown): B x max_seqlen rows = a dense
-// batch, which takes the paired-row-block forward
-static thread_local int64_t tl_fwd_tokens = 0;
-// attention bias of the call in flight on this thread (set by the *_rab entry points)
-struct RabCall { const uint16_t* rab = nullptr; int64_t rb = 0, rh = 0, rr = 0; uint16_t* drab = nullptr; int64_t db = 0, dh = 0, dr = 0;
-                 const int32_t* func = nullptr; int64_t fh = 0, fp = 0; int nf = 0; float fneg = 0.f;
-                 void* kvis = nullptr; int64_t kvis_bytes = 0; };   // (backward: room for the key-block table of the func masks)
-static thread_local RabCall tl_rab;
 static int window_skip() {   // MI355_HSTU_WSKIP=0: keep the full tile loops under a window (A/B tests of the band clipping)
   static const int v = [] { const char* e = getenv("MI355_HSTU_WSKIP"); return e ? atoi(e) != 0 : 1; }();
   return v;
@@ -3932,26 +3860,279 @@ static int64_t xch_tiles_bound(int64_t batch, int64_t num_heads, int64_t ng, int
   const int64_t jag = total_tokens > 0 ? (((total_tokens + 31) / 32 + batch) * umax + ng - 1) / ng : dense;
   return num_heads * (jag < dense ? jag : dense);
 }
+
+// ---- the one-shot channels of the ABI, the only state a call finds on its thread: the token hints (mi355_hstu_attn_fwd_hint_tokens,
+// mi355_hstu_attn_bwd_hint_tokens) and the strides of dq / dk / dv (mi355_hstu_attn_bwd_bind_grad_strides).  Every entry point takes
+// those of its direction as its first statement (forward_call / backward_call), in front of every check and every early return:
+// none of them outlives the call it was set for, however that call ends.
+// rows of q of the NEXT forward call on this thread (0 = unknown): B x max_seqlen rows = a dense batch, which takes the
+// paired-row-block forward
+static thread_local int64_t tl_fwd_tokens = 0;
 extern "C" int64_t mi355_hstu_attn_bwd_take_hint_(void);
 extern "C" int mi355_hstu_attn_bwd_take_grad_strides_(int64_t* strides);
-// The strides of dq / dk / dv for the backward entered on this thread: what mi355_hstu_attn_bwd_bind_grad_strides left (taken, so
-// the binding is gone from here on whatever the call does next), else the contiguous [T, H, D] layout.
-struct GradStrides { int64_t s[6]; bool bound; };
-static GradStrides take_grad_strides(int64_t num_heads, int64_t head_dim) {
-  GradStrides g;
-  g.bound = mi355_hstu_attn_bwd_take_grad_strides_(g.s) != 0;
-  if (!g.bound)
-    for (int i = 0; i < 6; i += 2) { g.s[i] = num_heads * head_dim; g.s[i + 1] = head_dim; }
-  return g;
+
+// Everything an attention call can be given; host only, never passed to a kernel.  An entry point fills one (whatever its
+// signature lacks stays null / 0) and hands it to hstu_forward, hstu_backward or hstu_backward_dq.
+struct HstuCall {
+  const void *q, *k, *v;
+  void* out; const void* dout;                   // forward / backward
+  int64_t q_row, k_row, v_row, o_row, q_head, k_head, v_head, o_head;   // (o: of out or of dout)
+  void *dq, *dk, *dv; int64_t grad[6];           // grad: row, head strides of dq, dk, dv -- what was bound, else contiguous [T, H, D]
+  const int32_t *cu_seqlens_q, *cu_seqlens_k;    // cu_seqlens_k null: the keys are the queries' tokens
+  int64_t batch, num_heads, head_dim, max_seqlen_q, max_seqlen_k;
+  const int32_t *num_contexts, *num_targets; int64_t group;
+  int causal, wl, wr;                            // the mask as the kernels take it: see set_mask
+  float alpha, scaling_seqlen;
+  const void* rab; int64_t rab_b, rab_h, rab_r;
+  void* drab; int64_t drab_b, drab_h, drab_r;
+  const int32_t* func; int64_t func_h, func_p; int n_func; float func_neg;
+  void* func_ws; int64_t func_ws_bytes;          // (backward: room for the key-block table of the func masks)
+  const void* kv_cache; const int32_t *page_offsets, *page_ids, *last_page_lens; int64_t page_size;
+  void* ws; int64_t ws_bytes;                    // the backward's P / dS exchange
+  int64_t tokens_hint;                           // total tokens of the batch as hinted, 0 = unknown
+  hipStream_t stream;
+};
+
+// what every signature has; group 1 and no window (a full mask) until the entry point says otherwise
+static HstuCall new_call(const void* q, const void* k, const void* v, int64_t q_row, int64_t k_row, int64_t v_row, int64_t o_row,
+                         int64_t q_head, int64_t k_head, int64_t v_head, int64_t o_head, const int32_t* cu_seqlens_q,
+                         const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen_q,
+                         int64_t max_seqlen_k, float alpha, float scaling_seqlen, hipStream_t stream) {
+  HstuCall c{};
+  c.q = q; c.k = k; c.v = v;
+  c.q_row = q_row; c.k_row = k_row; c.v_row = v_row; c.o_row = o_row;
+  c.q_head = q_head; c.k_head = k_head; c.v_head = v_head; c.o_head = o_head;
+  c.cu_seqlens_q = cu_seqlens_q; c.cu_seqlens_k = cu_seqlens_k;
+  c.batch = batch; c.num_heads = num_heads; c.head_dim = head_dim; c.max_seqlen_q = max_seqlen_q; c.max_seqlen_k = max_seqlen_k;
+  c.group = 1; c.wl = c.wr = -1;
+  c.alpha = alpha; c.scaling_seqlen = scaling_seqlen; c.stream = stream;
+  return c;
 }
-static bool grad_strides_ok(const GradStrides& g, int64_t head_dim) {
-  for (int i = 0; i < 6; ++i)
-    if (g.s[i] % 8 != 0 || g.s[i] < 0 || g.s[i] > INT32_MAX || ((i & 1) && g.s[i] < head_dim)) return false;
-  return true;
+// a forward's record, with the forward hint of this thread taken
+template <typename... Base>
+static HstuCall forward_call(void* out, Base... base) {
+  HstuCall c = new_call(base...);
+  c.out = out;
+  c.tokens_hint = tl_fwd_tokens;
+  tl_fwd_tokens = 0;
+  return c;
 }
-// The entry points that check arguments of their own in front of mi355_hstu_attn_bwd hold one of these: a binding such a check
-// returned past is dropped on the way out (the inner call has taken it otherwise and this finds nothing).
-struct GradStridesDrop { ~GradStridesDrop() { int64_t s[6]; mi355_hstu_attn_bwd_take_grad_strides_(s); } };
+// a backward's record, with the backward hint and the stride binding of this thread taken
+template <typename... Base>
+static HstuCall backward_call(const void* dout, void* dq, void* dk, void* dv, Base... base) {
+  HstuCall c = new_call(base...);
+  c.dout = dout; c.dq = dq; c.dk = dk; c.dv = dv;
+  c.tokens_hint = mi355_hstu_attn_bwd_take_hint_();
+  if (!mi355_hstu_attn_bwd_take_grad_strides_(c.grad))
+    for (int i = 0; i < 6; i += 2) { c.grad[i] = c.num_heads * c.head_dim; c.grad[i + 1] = c.head_dim; }
+  return c;
+}
+
+// The mask of a call given as window_size = (left, right) of hstu_attn_varlen_func (hstu_api.cpp:154-165: a negative side is
+// unbounded; (-1, 0) is causal, (-1, -1) full, else a local window: query i sees keys i - left .. i + right), in the kernels'
+// terms: right == 0 is what `causal` says (the causal tile loops apply), so wr carries the other values only.  Contextual / target
+// rows (set before this, where the signature has them) go with the plain causal mask alone (hstu_attn_interface.py:238-245).
+static int set_mask(HstuCall& c, int64_t left, int64_t right) {
+  MI355_CHECK_ARG(left >= -1 && right >= -1 && left < (1 << 30) && right < (1 << 30), "bad window");
+  MI355_CHECK_ARG(!(c.num_contexts || c.num_targets) || (left == -1 && right == 0),
+                  "contextual / target masks require the causal mask (-1, 0)");
+  c.causal = right == 0 ? 1 : 0;
+  c.wl = (int)left;
+  c.wr = right == 0 ? -1 : (int)right;
+  return MI355_OK;
+}
+
+// the checks every call makes.  kBwdDq: the entry point makes checks of its own BEHIND these, set_mask among them, so the mask is
+// not yet there to be held against the contextual / target rows.
+enum CallKind { kFwd, kBwd, kBwdDq };
+static int check_call(const HstuCall& c, CallKind kind) {
+  MI355_CHECK_ARG(c.head_dim == 32 || c.head_dim == 64 || c.head_dim == 128 || c.head_dim == 256,
+                  "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
+  if (kind != kFwd) {
+    bool ok = true;
+    for (int i = 0; i < 6; ++i) {
+      const int64_t s = c.grad[i];
+      ok = ok && s % 8 == 0 && s >= 0 && s <= INT32_MAX && (!(i & 1) || s >= c.head_dim);
+    }
+    MI355_CHECK_ARG(ok, "bound dq/dk/dv strides must be multiples of 8 elements in [0, 2^31), the head strides >= head_dim");
+  }
+  MI355_CHECK_ARG(c.group >= 1, "target_group_size must be >= 1");
+  MI355_CHECK_ARG(kind == kBwdDq || c.causal || (!c.num_contexts && !c.num_targets), "contextual / target masks require causal attention");
+  MI355_CHECK_ARG(c.scaling_seqlen > 0.f, "scaling_seqlen must be positive");
+  const bool qkv8 = c.q_row % 8 == 0 && c.k_row % 8 == 0 && c.v_row % 8 == 0 && c.q_head % 8 == 0 && c.k_head % 8 == 0 && c.v_head % 8 == 0;
+  if (kind == kFwd) {
+    MI355_CHECK_ARG(qkv8 && c.o_row % 4 == 0 && c.o_head % 4 == 0, "q/k/v strides must be multiples of 8 elements (16-byte rows)");
+    MI355_CHECK_ARG(!c.kv_cache || (c.cu_seqlens_k && c.page_offsets && c.page_ids && c.last_page_lens && c.page_size > 0),
+                    "a paged cache needs cu_seqlens_k, page_offsets, page_ids, last_page_lens and page_size");
+  } else {
+    MI355_CHECK_ARG(qkv8 && c.o_row % 8 == 0 && c.o_head % 8 == 0, "q/k/v/dout strides must be multiples of 8 elements (16-byte rows)");
+  }
+  return MI355_OK;
+}
+
+// the kernels' arguments of a call: the forward's, and the part of a backward's that every backward shares
+static void fill(AttnArgs& a, const HstuCall& c) {
+  a.q = (const uint16_t*)c.q; a.k = (const uint16_t*)c.k; a.v = (const uint16_t*)c.v; a.out = (uint16_t*)c.out;
+  a.q_row = c.q_row; a.k_row = c.k_row; a.v_row = c.v_row; a.o_row = c.o_row;
+  a.q_head = c.q_head; a.k_head = c.k_head; a.v_head = c.v_head; a.o_head = c.o_head;
+  a.cu_seqlens = c.cu_seqlens_q; a.num_contexts = c.num_contexts; a.num_targets = c.num_targets;
+  a.H = (int)c.num_heads; a.causal = c.causal; a.group = (int)c.group;
+  a.wl = c.wl; a.wr = c.wr; a.wskip = window_skip(); a.rot = -(int)c.num_heads; a.colmajor = 1; a.max_len = (int)c.max_seqlen_q;
+  a.rab = (const uint16_t*)c.rab; a.rab_b = c.rab_b; a.rab_h = c.rab_h; a.rab_r = c.rab_r;
+  a.func = c.func; a.func_h = c.func_h; a.func_p = c.func_p; a.n_func = c.n_func; a.func_neg = c.func_neg;
+  a.alpha = c.alpha; a.inv_scale = 1.0f / c.scaling_seqlen;
+  a.cu_seqlens_k = c.cu_seqlens_k; a.kv_cache = (const uint16_t*)c.kv_cache; a.page_offsets = c.page_offsets; a.page_ids = c.page_ids;
+  a.last_page_lens = c.last_page_lens; a.page_size = (int)c.page_size;
+}
+static void fill(BwdAttnArgs& g, const HstuCall& c) {
+  fill(g.f, c);
+  g.f.o_row = g.f.o_head = 0;   // (no out: the record's o strides are dout's)
+  g.dout = (const uint16_t*)c.dout; g.do_row = c.o_row; g.do_head = c.o_head;
+  g.dq = (uint16_t*)c.dq; g.dk = (uint16_t*)c.dk; g.dv = (uint16_t*)c.dv;
+  const int64_t* s = c.grad;
+  g.dq_row = (int)s[0]; g.dq_head = (int)s[1]; g.dk_row = (int)s[2]; g.dk_head = (int)s[3]; g.dv_row = (int)s[4]; g.dv_head = (int)s[5];
+  g.ng = (int)((c.max_seqlen_k + 31) / 32);
+  g.drab = (uint16_t*)c.drab; g.drab_b = c.drab_b; g.drab_h = c.drab_h; g.drab_r = c.drab_r;
+}
+
+static int hstu_forward(const HstuCall& c) {
+  if (const int rc = check_call(c, kFwd)) return rc;
+  if (c.batch == 0 || c.max_seqlen_q == 0) return MI355_OK;
+  AttnArgs a{};
+  fill(a, c);
+  const int B = (int)c.batch, max_q = (int)c.max_seqlen_q;
+  // round 4: two waves per SIMD, S waves + O waves (hook 5: the one-kind kernel)
+  // (`func` masks of up to two bands ride the 64-rows-per-wave forward at every length; longer function lists keep the one-kind kernel)
+  if (fwd_hook() != 5 && c.head_dim == 256 && !a.kv_cache && !a.rab && (!a.func || a.n_func <= 5))
+    return launch_fwd_pc<256>(a, B, max_q, c.stream, !c.cu_seqlens_k && c.tokens_hint == c.batch * c.max_seqlen_q);
+  switch (c.head_dim) {
+    case 32: return launch_fwd<32>(a, B, max_q, c.stream);
+    case 64: return launch_fwd<64>(a, B, max_q, c.stream);
+    case 128: return launch_fwd<128>(a, B, max_q, c.stream);
+    default: return launch_fwd<256>(a, B, max_q, c.stream);
+  }
+}
+
+// pinned host word the plan kernel writes when its plan needs more chunk passes than the host launched (see the kernel)
+static int* plan_err_word() {
+  static int* w = nullptr;
+  static bool tried = false;
+  if (!tried) {
+    tried = true;
+    if (hipHostMalloc((void**)&w, sizeof(int), hipHostMallocMapped) == hipSuccess && w) *w = 0; else w = nullptr;
+  }
+  return w;
+}
+
+// the backward of self attention over contiguous keys (max_seqlen_q = max_seqlen_k, no cu_seqlens_k)
+static int hstu_backward(const HstuCall& c) {
+  if (const int rc = check_call(c, kBwd)) return rc;
+  const int64_t batch = c.batch, num_heads = c.num_heads, head_dim = c.head_dim, max_seqlen = c.max_seqlen_k;
+  if (batch == 0 || max_seqlen == 0) return MI355_OK;
+  if (int* ew = plan_err_word()) {
+    if (*ew) {
+      *ew = 0;
+      mi355_set_error("an earlier hstu backward planned more exchange chunks than were launched (token hint of another batch?): "
+                      "its gradients are incomplete");
+      return MI355_EINVAL;
+    }
+  }
+  BwdAttnArgs g{};
+  fill(g, c);
+  const AttnArgs& a = g.f;
+  if (a.func && c.func_ws && a.wskip) {
+    // the query rows that reach every 128-key block, for the key-major passes (the query-major pass derives its reach in place)
+    // (table of total_tokens / 128 + batch + 1 entries per function set; a key block whose entry lies beyond the buffer is simply
+    //  not clipped -- both kernels check the index)
+    // layout: [gext: nfh x 4 slots int4 | kvis: nfh x slots int2] = 72 bytes per slot and function set
+    const int64_t nfh = a.func_h ? num_heads : 1;
+    const int64_t slots = c.func_ws_bytes / 72 / nfh;
+    if (slots > 0 && ((uintptr_t)c.func_ws & 15) == 0) {
+      const size_t sm = 4 * (size_t)((max_seqlen + 31) / 32) * sizeof(int);
+      int4* gext = (int4*)c.func_ws;
+      int2* kvis = (int2*)(gext + nfh * 4 * slots);
+      hipLaunchKernelGGL(hstu_func_kvis_kernel, dim3((unsigned)batch, (unsigned)nfh), dim3(256), sm, c.stream, a, (int)nfh, kvis, slots, gext);
+      g.func_kvis = kvis; g.func_kvis_h = slots; g.func_gext = gext;
+    }
+  }
+  int nchunks = 1;
+  {
+    const int64_t need = mi355_hstu_attn_bwd_ds_bytes(batch, num_heads, head_dim, max_seqlen);
+    const int64_t regions = xch_regions(head_dim), units = batch * num_heads, hdr = xch_plan_header(units);
+    const int64_t udense = (int64_t)g.ng * g.ng;
+    // plain causal mask: the sub-tiles above the diagonal do not exist in the chunked layout (see BwdAttnArgs::tri)
+    g.tri = (c.causal && !c.num_contexts && c.wl < 0 && c.wr < 0 && !c.rab && !c.func) ? 1 : 0;
+    const int64_t umax = xch_unit_tiles(g.ng, g.tri);
+    if (need > 0 && c.ws && c.ws_bytes >= need && ((uintptr_t)c.ws & 15) == 0) {
+      // the dense layout: everything in one pass
+      g.ds_ws = (uint16_t*)c.ws;
+      const int64_t one = batch * num_heads * udense * 2048;
+      if (need >= 2 * one && head_dim >= 128) g.p_ws = (uint16_t*)((uint8_t*)c.ws + one);
+    } else if (need > 0 && c.ws && ((uintptr_t)c.ws & 255) == 0 && !c.rab && (!c.func || (head_dim == 256 && c.n_func <= 5)) &&
+               c.ws_bytes > hdr && (c.ws_bytes - hdr) / regions / 2048 >= 2 * umax) {
+      // the jagged, chunked layout: [plan_base | plan_chunk | nchunks | dS region | P region]
+      const int64_t cap_tiles = (c.ws_bytes - hdr) / regions / 2048;
+      uint8_t* w = (uint8_t*)c.ws;
+      int64_t* base = (int64_t*)w;
+      int32_t* chunk = (int32_t*)(w + (units * 8 + 255) / 256 * 256);
+      int32_t* nch = (int32_t*)(w + hdr - 256);
+      g.plan_base = base; g.plan_chunk = chunk;
+      g.ds_ws = (uint16_t*)(w + hdr);
+      if (regions == 2) g.p_ws = (uint16_t*)(w + hdr + cap_tiles * 2048);
+      // chunks the greedy cut can need at most: every chunk but the last holds more than cap_tiles - umax tiles
+      const int64_t bound = xch_tiles_bound(batch, num_heads, g.ng, c.tokens_hint, g.tri);
+      nchunks = (int)((bound + (cap_tiles - umax)) / (cap_tiles - umax + 1));
+      // (round 5) a buffer as large as the bound itself holds every unit in ONE chunk: the formula above, which only knows that a
+      // chunk but the last holds more than cap - umax tiles, still said two -- and every jagged backward under the cap launched a
+      // second, empty set of three kernels (14 + 7 + 7 us at C4, profiles/r04_step_timeline.txt)
+      if (bound <= cap_tiles) nchunks = 1;
+      if (nchunks < 1) nchunks = 1;
+      if (nchunks > units) nchunks = (int)units;
+      hipLaunchKernelGGL(hstu_bwd_plan_kernel, dim3(1), dim3(256), 0, c.stream, c.cu_seqlens_q, (int)batch, (int)num_heads, cap_tiles, g.tri,
+                         base, chunk, nch, nchunks, plan_err_word());
+    }
+  }
+  for (int ch = 0; ch < nchunks; ++ch) {
+    g.chunk = ch;
+    int rc;
+    switch (head_dim) {
+      case 32: rc = launch_bwd<32>(g, (int)batch, (int)max_seqlen, c.stream); break;
+      case 64: rc = launch_bwd<64>(g, (int)batch, (int)max_seqlen, c.stream); break;
+      case 128: rc = launch_bwd<128>(g, (int)batch, (int)max_seqlen, c.stream); break;
+      default: rc = launch_bwd<256>(g, (int)batch, (int)max_seqlen, c.stream); break;
+    }
+    if (rc != MI355_OK) return rc;
+  }
+  return MI355_OK;
+}
+
+// Delta-q backward (hstu_bwd.h:98: actual_seqlen_offset = actual_seqlen_k - actual_seqlen_q in every tile bound and mask; the
+// reference's kernel tests differentiate such calls, corelib/hstu/test.py:667-720).  The queries of sequence b -- rows
+// cu_seqlens_q[b] .. of q / dout / dq -- are the LAST Lq of its Lk keys (rows cu_seqlens_k[b] .. of k / v / dk / dv), every mask and
+// the bias are taken at the absolute positions Lk - Lq + r.  The recomputing passes, no scratch; every row of dq / dk / dv is
+// written (keys no query reaches: zeros).  Lq > Lk in a sequence is visible on the device only and undefined, as in the forward:
+// the passes touch nothing of that sequence and its gradient rows stay unwritten.  (The caller has made the checks.)
+static int hstu_backward_dq(const HstuCall& c) {
+  if (c.batch == 0 || c.max_seqlen_k == 0) return MI355_OK;
+  BwdAttnArgs g{};
+  fill(g, c);
+  g.f.rot = 0; g.f.colmajor = 0; g.f.max_len = (int)c.max_seqlen_k;   // blocks map to (sequence, head) over the KEYS' extent
+  const int B = (int)c.batch, mq = (int)c.max_seqlen_q, mk = (int)c.max_seqlen_k;
+  if (c.rab) {
+    switch (c.head_dim) {
+      case 32: return launch_bwd_dq<32, true>(g, B, mq, mk, c.stream);
+      case 64: return launch_bwd_dq<64, true>(g, B, mq, mk, c.stream);
+      case 128: return launch_bwd_dq<128, true>(g, B, mq, mk, c.stream);
+      default: return launch_bwd_dq<256, true>(g, B, mq, mk, c.stream);
+    }
+  }
+  switch (c.head_dim) {
+    case 32: return launch_bwd_dq<32, false>(g, B, mq, mk, c.stream);
+    case 64: return launch_bwd_dq<64, false>(g, B, mq, mk, c.stream);
+    case 128: return launch_bwd_dq<128, false>(g, B, mq, mk, c.stream);
+    default: return launch_bwd_dq<256, false>(g, B, mq, mk, c.stream);
+  }
+}
 
 extern "C" {
 #if HSTU_TIMING && !HSTU_F16
@@ -3969,10 +4150,11 @@ int HSTU_FN(mi355_hstu_attn_fwd)(const void* q, const void* k, const void* v, vo
                         int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
                         const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size, int causal,
                         float alpha, float scaling_seqlen, hipStream_t stream) {
-  return HSTU_FN(mi355_hstu_attn_fwd_kv)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                k_head_stride, v_head_stride, o_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim,
-                                max_seqlen, num_contexts, num_targets, target_group_size, causal, alpha, scaling_seqlen,
-                                nullptr, nullptr, nullptr, nullptr, 0, stream);
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen, max_seqlen,
+                            alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size; c.causal = causal;
+  return hstu_forward(c);
 }
 
 // Inference forward: queries may be the tail of a longer key sequence (cu_seqlens_k, "delta-q") and the keys / values
@@ -3986,41 +4168,12 @@ int HSTU_FN(mi355_hstu_attn_fwd_kv)(const void* q, const void* k, const void* v,
                            int64_t target_group_size, int causal, float alpha, float scaling_seqlen, const void* kv_cache,
                            const int32_t* page_offsets, const int32_t* page_ids, const int32_t* last_page_lens,
                            int64_t page_size, hipStream_t stream) {
-  MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
-                  "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
-  MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
-  MI355_CHECK_ARG(causal || (!num_contexts && !num_targets), "contextual / target masks require causal attention");
-  MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
-  MI355_CHECK_ARG(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && o_row_stride % 4 == 0 &&
-                      q_head_stride % 8 == 0 && k_head_stride % 8 == 0 && v_head_stride % 8 == 0 && o_head_stride % 4 == 0,
-                  "q/k/v strides must be multiples of 8 elements (16-byte rows)");
-  MI355_CHECK_ARG(!kv_cache || (cu_seqlens_k && page_offsets && page_ids && last_page_lens && page_size > 0),
-                  "a paged cache needs cu_seqlens_k, page_offsets, page_ids, last_page_lens and page_size");
-  if (batch == 0 || max_seqlen_q == 0) return MI355_OK;
-  AttnArgs a{};
-  a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = (uint16_t*)out;
-  a.q_row = q_row_stride; a.k_row = k_row_stride; a.v_row = v_row_stride; a.o_row = o_row_stride;
-  a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = o_head_stride;
-  a.cu_seqlens = cu_seqlens_q; a.num_contexts = num_contexts; a.num_targets = num_targets;
-  a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
-  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = -(int)num_heads; a.colmajor = 1; a.max_len = (int)max_seqlen_q;
-  a.rab = tl_rab.rab; a.rab_b = tl_rab.rb; a.rab_h = tl_rab.rh; a.rab_r = tl_rab.rr;
-  a.func = tl_rab.func; a.func_h = tl_rab.fh; a.func_p = tl_rab.fp; a.n_func = tl_rab.nf; a.func_neg = tl_rab.fneg;
-  a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
-  a.cu_seqlens_k = cu_seqlens_k; a.kv_cache = (const uint16_t*)kv_cache; a.page_offsets = page_offsets; a.page_ids = page_ids;
-  a.last_page_lens = last_page_lens; a.page_size = (int)page_size;
-  static const int use_pc = !(getenv("MI355_HSTU_FWD") && atoi(getenv("MI355_HSTU_FWD")) == 5);   // round 4: two waves per SIMD, S waves + O waves (hook 5: the one-kind kernel)
-  const int64_t fwd_tokens = tl_fwd_tokens;
-  tl_fwd_tokens = 0;
-  // (`func` masks of up to two bands ride the 64-rows-per-wave forward at every length; longer function lists keep the one-kind kernel)
-  if (use_pc && head_dim == 256 && !a.kv_cache && !a.rab && (!a.func || a.n_func <= 5))
-    return launch_fwd_pc<256>(a, (int)batch, (int)max_seqlen_q, stream, !cu_seqlens_k && fwd_tokens == batch * max_seqlen_q);
-  switch (head_dim) {
-    case 32: return launch_fwd<32>(a, (int)batch, (int)max_seqlen_q, stream);
-    case 64: return launch_fwd<64>(a, (int)batch, (int)max_seqlen_q, stream);
-    case 128: return launch_fwd<128>(a, (int)batch, (int)max_seqlen_q, stream);
-    default: return launch_fwd<256>(a, (int)batch, (int)max_seqlen_q, stream);
-  }
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim, max_seqlen_q, 0,
+                            alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size; c.causal = causal;
+  c.kv_cache = kv_cache; c.page_offsets = page_offsets; c.page_ids = page_ids; c.last_page_lens = last_page_lens; c.page_size = page_size;
+  return hstu_forward(c);
 }
 
 // rows of q of the NEXT forward call on this thread (the reference's forward signature does not carry them): a batch of
@@ -4104,8 +4257,8 @@ int64_t mi355_hstu_attn_bwd_ds_bytes_capped(int64_t batch, int64_t num_heads, in
   const int64_t bytes = want < cap_bytes ? want : cap_bytes;
   return (bytes - hdr) / regions / 2048 >= 2 * xch_unit_tiles(ng, tri) ? bytes : 0;
 }
-// total tokens of the NEXT mi355_hstu_attn_bwd call on this thread (its signature, the reference's, does not carry them):
-// tightens the number of chunk passes a capped workspace is walked in; 0 / not set = the dense bound
+// total tokens of the NEXT backward call on this thread (the signatures, the reference's, do not carry them; taken on entry by
+// every backward entry point): tightens the number of chunk passes a capped workspace is walked in; 0 / not set = the dense bound
 static thread_local int64_t tl_bwd_tokens = 0;
 void mi355_hstu_attn_bwd_hint_tokens(int64_t total_tokens) { tl_bwd_tokens = total_tokens; }
 int64_t mi355_hstu_attn_bwd_take_hint_(void) { const int64_t t = tl_bwd_tokens; tl_bwd_tokens = 0; return t; }   // (internal: both translation units)
@@ -4129,17 +4282,6 @@ int mi355_hstu_attn_bwd_take_grad_strides_(int64_t* strides) {   // (internal: b
 
 #endif
 
-// pinned host word the plan kernel writes when its plan needs more chunk passes than the host launched (see the kernel)
-static int* plan_err_word() {
-  static int* w = nullptr;
-  static bool tried = false;
-  if (!tried) {
-    tried = true;
-    if (hipHostMalloc((void**)&w, sizeof(int), hipHostMallocMapped) == hipSuccess && w) *w = 0; else w = nullptr;
-  }
-  return w;
-}
-
 // hstu_varlen_bwd (corelib/hstu/csrc/hstu_attn/hstu_api.cpp:525-719).  dq, dk, dv: bf16 [total, H, d], contiguous unless
 // mi355_hstu_attn_bwd_bind_grad_strides gave this call their strides.
 int HSTU_FN(mi355_hstu_attn_bwd)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
@@ -4148,132 +4290,26 @@ int HSTU_FN(mi355_hstu_attn_bwd)(const void* dout, const void* q, const void* k,
                         const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
                         const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size, int causal,
                         float alpha, float scaling_seqlen, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  const GradStrides gs = take_grad_strides(num_heads, head_dim);
-  MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
-                  "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
-  MI355_CHECK_ARG(grad_strides_ok(gs, head_dim),
-                  "bound dq/dk/dv strides must be multiples of 8 elements in [0, 2^31), the head strides >= head_dim");
-  MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
-  MI355_CHECK_ARG(causal || (!num_contexts && !num_targets), "contextual / target masks require causal attention");
-  MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
-  MI355_CHECK_ARG(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && do_row_stride % 8 == 0 &&
-                      q_head_stride % 8 == 0 && k_head_stride % 8 == 0 && v_head_stride % 8 == 0 && do_head_stride % 8 == 0,
-                  "q/k/v/dout strides must be multiples of 8 elements (16-byte rows)");
-  if (batch == 0 || max_seqlen == 0) return MI355_OK;
-  if (int* ew = plan_err_word()) {
-    if (*ew) {
-      *ew = 0;
-      mi355_set_error("an earlier hstu backward planned more exchange chunks than were launched (token hint of another batch?): "
-                      "its gradients are incomplete");
-      return MI355_EINVAL;
-    }
-  }
-  BwdAttnArgs g{};
-  AttnArgs& a = g.f;
-  a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = nullptr;
-  a.q_row = q_row_stride; a.k_row = k_row_stride; a.v_row = v_row_stride; a.o_row = 0;
-  a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = 0;
-  a.cu_seqlens = cu_seqlens; a.num_contexts = num_contexts; a.num_targets = num_targets;
-  a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
-  a.wl = tl_wl; a.wr = tl_wr; a.wskip = window_skip(); a.rot = -(int)num_heads; a.colmajor = 1; a.max_len = (int)max_seqlen;
-  a.rab = tl_rab.rab; a.rab_b = tl_rab.rb; a.rab_h = tl_rab.rh; a.rab_r = tl_rab.rr;
-  a.func = tl_rab.func; a.func_h = tl_rab.fh; a.func_p = tl_rab.fp; a.n_func = tl_rab.nf; a.func_neg = tl_rab.fneg;
-  a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
-  g.dout = (const uint16_t*)dout; g.do_row = do_row_stride; g.do_head = do_head_stride;
-  g.dq = (uint16_t*)dq; g.dk = (uint16_t*)dk; g.dv = (uint16_t*)dv;
-  g.dq_row = (int)gs.s[0]; g.dq_head = (int)gs.s[1]; g.dk_row = (int)gs.s[2]; g.dk_head = (int)gs.s[3]; g.dv_row = (int)gs.s[4]; g.dv_head = (int)gs.s[5];
-  g.ds_ws = nullptr; g.ng = (int)((max_seqlen + 31) / 32); g.bq_kv = 32;
-  g.drab = tl_rab.drab; g.drab_b = tl_rab.db; g.drab_h = tl_rab.dh; g.drab_r = tl_rab.dr;
-  g.plan_base = nullptr; g.plan_chunk = nullptr; g.chunk = 0;
-  g.func_kvis = nullptr; g.func_kvis_h = 0; g.func_gext = nullptr;
-  const int64_t tokens_hint = mi355_hstu_attn_bwd_take_hint_();
-  if (a.func && tl_rab.kvis && a.wskip) {
-    // the query rows that reach every 128-key block, for the key-major passes (the query-major pass derives its reach in place)
-    // (table of total_tokens / 128 + batch + 1 entries per function set; a key block whose entry lies beyond the buffer is simply
-    //  not clipped -- both kernels check the index)
-    // layout: [gext: nfh x 4 slots int4 | kvis: nfh x slots int2] = 72 bytes per slot and function set
-    const int64_t nfh = a.func_h ? num_heads : 1;
-    const int64_t slots = tl_rab.kvis_bytes / 72 / nfh;
-    if (slots > 0 && ((uintptr_t)tl_rab.kvis & 15) == 0) {
-      const size_t sm = 4 * (size_t)((max_seqlen + 31) / 32) * sizeof(int);
-      int4* gext = (int4*)tl_rab.kvis;
-      int2* kvis = (int2*)(gext + nfh * 4 * slots);
-      hipLaunchKernelGGL(hstu_func_kvis_kernel, dim3((unsigned)batch, (unsigned)nfh), dim3(256), sm, stream, a, (int)nfh, kvis, slots, gext);
-      g.func_kvis = kvis; g.func_kvis_h = slots; g.func_gext = gext;
-    }
-  }
-  int nchunks = 1;
-  {
-    const int64_t need = mi355_hstu_attn_bwd_ds_bytes(batch, num_heads, head_dim, max_seqlen);
-    const int64_t regions = xch_regions(head_dim), units = batch * num_heads, hdr = xch_plan_header(units);
-    const int64_t udense = (int64_t)g.ng * g.ng;
-    // plain causal mask: the sub-tiles above the diagonal do not exist in the chunked layout (see BwdAttnArgs::tri)
-    g.tri = (causal && !num_contexts && tl_wl < 0 && tl_wr < 0 && !tl_rab.rab && !tl_rab.func) ? 1 : 0;
-    const int64_t umax = xch_unit_tiles(g.ng, g.tri);
-    g.p_ws = nullptr;
-    if (need > 0 && workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0) {
-      // the dense layout: everything in one pass
-      g.ds_ws = (uint16_t*)workspace;
-      const int64_t one = batch * num_heads * udense * 2048;
-      if (need >= 2 * one && head_dim >= 128) g.p_ws = (uint16_t*)((uint8_t*)workspace + one);
-    } else if (need > 0 && workspace && ((uintptr_t)workspace & 255) == 0 && !tl_rab.rab &&
-               (!tl_rab.func || (head_dim == 256 && tl_rab.nf <= 5)) && workspace_bytes > hdr &&
-               (workspace_bytes - hdr) / regions / 2048 >= 2 * umax) {
-      // the jagged, chunked layout: [plan_base | plan_chunk | nchunks | dS region | P region]
-      const int64_t cap_tiles = (workspace_bytes - hdr) / regions / 2048;
-      uint8_t* w = (uint8_t*)workspace;
-      int64_t* base = (int64_t*)w;
-      int32_t* chunk = (int32_t*)(w + (units * 8 + 255) / 256 * 256);
-      int32_t* nch = (int32_t*)(w + hdr - 256);
-      g.plan_base = base; g.plan_chunk = chunk;
-      g.ds_ws = (uint16_t*)(w + hdr);
-      if (regions == 2) g.p_ws = (uint16_t*)(w + hdr + cap_tiles * 2048);
-      // chunks the greedy cut can need at most: every chunk but the last holds more than cap_tiles - umax tiles
-      const int64_t bound = xch_tiles_bound(batch, num_heads, g.ng, tokens_hint, g.tri);
-      nchunks = (int)((bound + (cap_tiles - umax)) / (cap_tiles - umax + 1));
-      // (round 5) a buffer as large as the bound itself holds every unit in ONE chunk: the formula above, which only knows that a
-      // chunk but the last holds more than cap - umax tiles, still said two -- and every jagged backward under the cap launched a
-      // second, empty set of three kernels (14 + 7 + 7 us at C4, profiles/r04_step_timeline.txt)
-      if (bound <= cap_tiles) nchunks = 1;
-      if (nchunks < 1) nchunks = 1;
-      if (nchunks > units) nchunks = (int)units;
-      hipLaunchKernelGGL(hstu_bwd_plan_kernel, dim3(1), dim3(256), 0, stream, cu_seqlens, (int)batch, (int)num_heads, cap_tiles, g.tri,
-                         base, chunk, nch, nchunks, plan_err_word());
-    }
-  }
-  for (int c = 0; c < nchunks; ++c) {
-    g.chunk = c;
-    int rc;
-    switch (head_dim) {
-      case 32: rc = launch_bwd<32>(g, (int)batch, (int)max_seqlen, stream); break;
-      case 64: rc = launch_bwd<64>(g, (int)batch, (int)max_seqlen, stream); break;
-      case 128: rc = launch_bwd<128>(g, (int)batch, (int)max_seqlen, stream); break;
-      default: rc = launch_bwd<256>(g, (int)batch, (int)max_seqlen, stream); break;
-    }
-    if (rc != MI355_OK) return rc;
-  }
-  return MI355_OK;
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen,
+                             max_seqlen, alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size; c.causal = causal;
+  c.ws = workspace; c.ws_bytes = workspace_bytes;
+  return hstu_backward(c);
 }
 
-
-// Local (sliding window) attention, window_size = (left, right) of hstu_attn_varlen_func (hstu_api.cpp:154-165: a negative
-// side is unbounded; (-1, 0) is causal, (-1, -1) full): query i sees keys i - left .. i + right.  No contextual / target
-// rows with a window (hstu_attn_interface.py:238-245), self attention only.
-static int window_causal(int64_t wl, int64_t wr) { return wr == 0 ? 1 : 0; }   // right == 0: the causal tile loops apply
-
+// Local (sliding window) attention, window_size = (left, right) as set_mask takes it.  No contextual / target rows with a window
+// (hstu_attn_interface.py:238-245), self attention only.
 int HSTU_FN(mi355_hstu_attn_fwd_window)(const void* q, const void* k, const void* v, void* out, int64_t q_row_stride,
                                int64_t k_row_stride, int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride,
                                int64_t k_head_stride, int64_t v_head_stride, int64_t o_head_stride, const int32_t* cu_seqlens,
                                int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen, int64_t window_left,
                                int64_t window_right, float alpha, float scaling_seqlen, hipStream_t stream) {
-  MI355_CHECK_ARG(window_left >= -1 && window_right >= -1 && window_left < (1 << 30) && window_right < (1 << 30), "bad window");
-  tl_wl = (int)window_left; tl_wr = window_right == 0 ? -1 : (int)window_right;   // (right == 0 is what `causal` already says)
-  const int rc = HSTU_FN(mi355_hstu_attn_fwd)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                     k_head_stride, v_head_stride, o_head_stride, cu_seqlens, batch, num_heads, head_dim,
-                                     max_seqlen, nullptr, nullptr, 1, window_causal(window_left, window_right), alpha,
-                                     scaling_seqlen, stream);
-  tl_wl = tl_wr = -1;
-  return rc;
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen, max_seqlen,
+                            alpha, scaling_seqlen, stream);
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  return hstu_forward(c);
 }
 
 // The inference forward (delta-q keys, paged cache) with a local attention window (hstu_fwd.h:104-131,463-470,516-545 compose
@@ -4285,14 +4321,12 @@ int HSTU_FN(mi355_hstu_attn_fwd_kv_window)(const void* q, const void* k, const v
                                   int64_t max_seqlen_q, int64_t window_left, int64_t window_right, float alpha,
                                   float scaling_seqlen, const void* kv_cache, const int32_t* page_offsets,
                                   const int32_t* page_ids, const int32_t* last_page_lens, int64_t page_size, hipStream_t stream) {
-  MI355_CHECK_ARG(window_left >= -1 && window_right >= -1 && window_left < (1 << 30) && window_right < (1 << 30), "bad window");
-  tl_wl = (int)window_left; tl_wr = window_right == 0 ? -1 : (int)window_right;
-  const int rc = HSTU_FN(mi355_hstu_attn_fwd_kv)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                        k_head_stride, v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads,
-                                        head_dim, max_seqlen_q, nullptr, nullptr, 1, window_causal(window_left, window_right), alpha,
-                                        scaling_seqlen, kv_cache, page_offsets, page_ids, last_page_lens, page_size, stream);
-  tl_wl = tl_wr = -1;
-  return rc;
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim, max_seqlen_q, 0,
+                            alpha, scaling_seqlen, stream);
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.kv_cache = kv_cache; c.page_offsets = page_offsets; c.page_ids = page_ids; c.last_page_lens = last_page_lens; c.page_size = page_size;
+  return hstu_forward(c);
 }
 
 int HSTU_FN(mi355_hstu_attn_bwd_window)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
@@ -4301,15 +4335,12 @@ int HSTU_FN(mi355_hstu_attn_bwd_window)(const void* dout, const void* q, const v
                                const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim,
                                int64_t max_seqlen, int64_t window_left, int64_t window_right, float alpha,
                                float scaling_seqlen, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  GradStridesDrop drop_unreached_binding;
-  MI355_CHECK_ARG(window_left >= -1 && window_right >= -1 && window_left < (1 << 30) && window_right < (1 << 30), "bad window");
-  tl_wl = (int)window_left; tl_wr = window_right == 0 ? -1 : (int)window_right;
-  const int rc = HSTU_FN(mi355_hstu_attn_bwd)(dout, q, k, v, dq, dk, dv, q_row_stride, k_row_stride, v_row_stride, do_row_stride,
-                                     q_head_stride, k_head_stride, v_head_stride, do_head_stride, cu_seqlens, batch, num_heads,
-                                     head_dim, max_seqlen, nullptr, nullptr, 1, window_causal(window_left, window_right), alpha,
-                                     scaling_seqlen, workspace, workspace_bytes, stream);
-  tl_wl = tl_wr = -1;
-  return rc;
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen,
+                             max_seqlen, alpha, scaling_seqlen, stream);
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.ws = workspace; c.ws_bytes = workspace_bytes;
+  return hstu_backward(c);
 }
 
 // Relative attention bias (`rab` / `has_drab` of hstu_attn_varlen_func; hstu_api.cpp:100-111,253-263,417-430,659-667).
@@ -4318,16 +4349,6 @@ int HSTU_FN(mi355_hstu_attn_bwd_window)(const void* dout, const void* q, const v
 // in hstu_attn_varlen_func: window (-1, 0) causal (contextual / target rows allowed), (-1, -1) full, else a local window.
 // Self attention over contiguous keys only.  drab (backward, nullable): bf16 with its own strides, one matrix per head,
 // zero-filled by the caller; receives d loss / d rab (= dS) at every position inside the sequences.
-static int rab_mask(int64_t wl, int64_t wr, const int32_t* nc, const int32_t* nt, int* causal) {
-  MI355_CHECK_ARG(wl >= -1 && wr >= -1 && wl < (1 << 30) && wr < (1 << 30), "bad window");
-  const bool local = !(wl == -1 && (wr == -1 || wr == 0));
-  MI355_CHECK_ARG(!(nc || nt) || (wl == -1 && wr == 0), "contextual / target masks require the causal mask (-1, 0)");
-  *causal = wr == 0 ? 1 : 0;
-  tl_wl = local ? (int)wl : -1;
-  tl_wr = (local && wr != 0) ? (int)wr : -1;
-  return MI355_OK;
-}
-
 int HSTU_FN(mi355_hstu_attn_fwd_rab)(const void* q, const void* k, const void* v, void* out, int64_t q_row_stride, int64_t k_row_stride,
                             int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride, int64_t k_head_stride,
                             int64_t v_head_stride, int64_t o_head_stride, const int32_t* cu_seqlens, int64_t batch,
@@ -4335,17 +4356,14 @@ int HSTU_FN(mi355_hstu_attn_fwd_rab)(const void* q, const void* k, const void* v
                             const int32_t* num_targets, int64_t target_group_size, int64_t window_left, int64_t window_right,
                             float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride,
                             int64_t rab_head_stride, int64_t rab_row_stride, hipStream_t stream) {
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen, max_seqlen,
+                            alpha, scaling_seqlen, stream);
   MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen, "rab must be [batch][heads or 1][max_seqlen][max_seqlen]");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  tl_rab = RabCall{(const uint16_t*)rab, rab_batch_stride, rab_head_stride, rab_row_stride, nullptr, 0, 0, 0};
-  const int rc = HSTU_FN(mi355_hstu_attn_fwd)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                     k_head_stride, v_head_stride, o_head_stride, cu_seqlens, batch, num_heads, head_dim,
-                                     max_seqlen, num_contexts, num_targets, target_group_size, causal, alpha, scaling_seqlen,
-                                     stream);
-  tl_rab = RabCall{};
-  tl_wl = tl_wr = -1;
-  return rc;
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  return hstu_forward(c);
 }
 
 // The inference forward (delta-q keys, paged cache) with a relative attention bias: rab[b][h][i][j] is indexed by ABSOLUTE positions
@@ -4359,17 +4377,15 @@ int HSTU_FN(mi355_hstu_attn_fwd_kv_rab)(const void* q, const void* k, const void
                                int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, const void* kv_cache,
                                const int32_t* page_offsets, const int32_t* page_ids, const int32_t* last_page_lens,
                                int64_t page_size, hipStream_t stream) {
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim, max_seqlen_q,
+                            max_seqlen_k, alpha, scaling_seqlen, stream);
   MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen_k, "rab must be [batch][heads or 1][max_seqlen_k][max_seqlen_k]");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  tl_rab = RabCall{(const uint16_t*)rab, rab_batch_stride, rab_head_stride, rab_row_stride, nullptr, 0, 0, 0};
-  const int rc = HSTU_FN(mi355_hstu_attn_fwd_kv)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                        k_head_stride, v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads,
-                                        head_dim, max_seqlen_q, num_contexts, num_targets, target_group_size, causal, alpha,
-                                        scaling_seqlen, kv_cache, page_offsets, page_ids, last_page_lens, page_size, stream);
-  tl_rab = RabCall{};
-  tl_wl = tl_wr = -1;
-  return rc;
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  c.kv_cache = kv_cache; c.page_offsets = page_offsets; c.page_ids = page_ids; c.last_page_lens = last_page_lens; c.page_size = page_size;
+  return hstu_forward(c);
 }
 
 int HSTU_FN(mi355_hstu_attn_bwd_rab)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
@@ -4380,31 +4396,22 @@ int HSTU_FN(mi355_hstu_attn_bwd_rab)(const void* dout, const void* q, const void
                             int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
                             int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
                             int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, hipStream_t stream) {
-  GradStridesDrop drop_unreached_binding;
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen,
+                             max_seqlen, alpha, scaling_seqlen, stream);
   MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen, "rab must be [batch][heads or 1][max_seqlen][max_seqlen]");
   MI355_CHECK_ARG(drab == nullptr || (drab_row_stride >= max_seqlen && drab_head_stride > 0),
                   "drab must hold one [max_seqlen][max_seqlen] matrix per head");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  tl_rab = RabCall{(const uint16_t*)rab, rab_batch_stride, rab_head_stride, rab_row_stride,
-                   (uint16_t*)drab, drab_batch_stride, drab_head_stride, drab_row_stride};
-  const int rc = HSTU_FN(mi355_hstu_attn_bwd)(dout, q, k, v, dq, dk, dv, q_row_stride, k_row_stride, v_row_stride, do_row_stride,
-                                     q_head_stride, k_head_stride, v_head_stride, do_head_stride, cu_seqlens, batch, num_heads,
-                                     head_dim, max_seqlen, num_contexts, num_targets, target_group_size, causal, alpha,
-                                     scaling_seqlen, nullptr, 0, stream);
-  tl_rab = RabCall{};
-  tl_wl = tl_wr = -1;
-  return rc;
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  c.drab = drab; c.drab_b = drab_batch_stride; c.drab_h = drab_head_stride; c.drab_r = drab_row_stride;
+  return hstu_backward(c);   // (no exchange with a bias: the recomputing passes)
 }
 
-// Delta-q backward (hstu_bwd.h:98: actual_seqlen_offset = actual_seqlen_k - actual_seqlen_q in every tile bound and mask; the
-// reference's kernel tests differentiate such calls, corelib/hstu/test.py:667-720).  The queries of sequence b -- rows
-// cu_seqlens_q[b] .. of q / dout / dq -- are the LAST Lq of its Lk keys (rows cu_seqlens_k[b] .. of k / v / dk / dv), every mask and
-// the bias are taken at the absolute positions Lk - Lq + r.  Mask as window_size: (-1, 0) causal (contextual / target rows
-// allowed), (-1, -1) full, otherwise a local window.  rab / drab nullable, [batch][heads or 1 / heads][max_seqlen_k][max_seqlen_k];
-// drab zero-filled by the caller (its rows in front of a sequence's first query stay zero).  The recomputing passes, no scratch;
-// every row of dq / dk / dv is written (keys no query reaches: zeros).  Lq > Lk in a sequence is visible on the device only and
-// undefined, as in the forward: the passes touch nothing of that sequence and its gradient rows stay unwritten.
+// The delta-q backward (hstu_backward_dq).  Mask as window_size: (-1, 0) causal (contextual / target rows allowed), (-1, -1) full,
+// otherwise a local window.  rab / drab nullable, [batch][heads or 1 / heads][max_seqlen_k][max_seqlen_k]; drab zero-filled by the
+// caller (its rows in front of a sequence's first query stay zero).  Its own checks come BEHIND the shared ones.
 int HSTU_FN(mi355_hstu_attn_bwd_kv)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
                            int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
                            int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
@@ -4414,56 +4421,20 @@ int HSTU_FN(mi355_hstu_attn_bwd_kv)(const void* dout, const void* q, const void*
                            float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride, int64_t rab_head_stride,
                            int64_t rab_row_stride, void* drab, int64_t drab_batch_stride, int64_t drab_head_stride,
                            int64_t drab_row_stride, hipStream_t stream) {
-  const GradStrides gs = take_grad_strides(num_heads, head_dim);
-  MI355_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128 || head_dim == 256,
-                  "head_dim must be one of 32, 64, 128, 256 (hstu_api.cpp:391)");
-  MI355_CHECK_ARG(grad_strides_ok(gs, head_dim),
-                  "bound dq/dk/dv strides must be multiples of 8 elements in [0, 2^31), the head strides >= head_dim");
-  MI355_CHECK_ARG(target_group_size >= 1, "target_group_size must be >= 1");
-  MI355_CHECK_ARG(scaling_seqlen > 0.f, "scaling_seqlen must be positive");
-  MI355_CHECK_ARG(q_row_stride % 8 == 0 && k_row_stride % 8 == 0 && v_row_stride % 8 == 0 && do_row_stride % 8 == 0 &&
-                      q_head_stride % 8 == 0 && k_head_stride % 8 == 0 && v_head_stride % 8 == 0 && do_head_stride % 8 == 0,
-                  "q/k/v/dout strides must be multiples of 8 elements (16-byte rows)");
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim,
+                             max_seqlen_q, max_seqlen_k, alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = check_call(c, kBwdDq)) return rc;
   MI355_CHECK_ARG(batch == 0 || (cu_seqlens_q && cu_seqlens_k), "cu_seqlens_q and cu_seqlens_k are required");
   MI355_CHECK_ARG(max_seqlen_q >= 0 && max_seqlen_q <= max_seqlen_k, "the queries are the last rows of the keys: max_seqlen_q <= max_seqlen_k (Lq <= Lk)");
   MI355_CHECK_ARG(rab == nullptr || rab_row_stride >= max_seqlen_k, "rab must be [batch][heads or 1][max_seqlen_k][max_seqlen_k]");
   MI355_CHECK_ARG(drab == nullptr || (rab != nullptr && drab_row_stride >= max_seqlen_k && drab_head_stride > 0),
                   "drab needs rab and must hold one [max_seqlen_k][max_seqlen_k] matrix per head");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  BwdAttnArgs g{};
-  AttnArgs& a = g.f;
-  a.wl = tl_wl; a.wr = tl_wr;
-  tl_wl = tl_wr = -1;
-  if (batch == 0 || max_seqlen_k == 0) return MI355_OK;
-  a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = nullptr;
-  a.q_row = q_row_stride; a.k_row = k_row_stride; a.v_row = v_row_stride; a.o_row = 0;
-  a.q_head = q_head_stride; a.k_head = k_head_stride; a.v_head = v_head_stride; a.o_head = 0;
-  a.cu_seqlens = cu_seqlens_q; a.cu_seqlens_k = cu_seqlens_k; a.num_contexts = num_contexts; a.num_targets = num_targets;
-  a.H = (int)num_heads; a.causal = causal; a.group = (int)target_group_size;
-  a.wskip = window_skip(); a.rot = 0; a.colmajor = 0; a.max_len = (int)max_seqlen_k;
-  a.rab = (const uint16_t*)rab; a.rab_b = rab_batch_stride; a.rab_h = rab_head_stride; a.rab_r = rab_row_stride;
-  a.alpha = alpha; a.inv_scale = 1.0f / scaling_seqlen;
-  g.dout = (const uint16_t*)dout; g.do_row = do_row_stride; g.do_head = do_head_stride;
-  g.dq = (uint16_t*)dq; g.dk = (uint16_t*)dk; g.dv = (uint16_t*)dv;
-  g.dq_row = (int)gs.s[0]; g.dq_head = (int)gs.s[1]; g.dk_row = (int)gs.s[2]; g.dk_head = (int)gs.s[3]; g.dv_row = (int)gs.s[4]; g.dv_head = (int)gs.s[5];
-  g.ng = (int)((max_seqlen_k + 31) / 32);
-  g.drab = (uint16_t*)drab; g.drab_b = drab_batch_stride; g.drab_h = drab_head_stride; g.drab_r = drab_row_stride;
-  const int B = (int)batch, mq = (int)max_seqlen_q, mk = (int)max_seqlen_k;
-  if (rab) {
-    switch (head_dim) {
-      case 32: return launch_bwd_dq<32, true>(g, B, mq, mk, stream);
-      case 64: return launch_bwd_dq<64, true>(g, B, mq, mk, stream);
-      case 128: return launch_bwd_dq<128, true>(g, B, mq, mk, stream);
-      default: return launch_bwd_dq<256, true>(g, B, mq, mk, stream);
-    }
-  }
-  switch (head_dim) {
-    case 32: return launch_bwd_dq<32, false>(g, B, mq, mk, stream);
-    case 64: return launch_bwd_dq<64, false>(g, B, mq, mk, stream);
-    case 128: return launch_bwd_dq<128, false>(g, B, mq, mk, stream);
-    default: return launch_bwd_dq<256, false>(g, B, mq, mk, stream);
-  }
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  c.drab = drab; c.drab_b = drab_batch_stride; c.drab_h = drab_head_stride; c.drab_r = drab_row_stride;
+  return hstu_backward_dq(c);
 }
 
 // Arbitrary mask functions (`func` of hstu_attn_varlen_func; hstu_api.cpp:170-180, applied in hstu_fwd.h:139-145, 493-556) read INSIDE
@@ -4481,19 +4452,16 @@ int HSTU_FN(mi355_hstu_attn_fwd_kv_func)(const void* q, const void* k, const voi
                                 int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
                                 const void* kv_cache, const int32_t* page_offsets, const int32_t* page_ids,
                                 const int32_t* last_page_lens, int64_t page_size, hipStream_t stream) {
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim, max_seqlen_q,
+                            max_seqlen_k, alpha, scaling_seqlen, stream);
   MI355_CHECK_ARG(func != nullptr && n_func >= 1 && (n_func & 1) == 1 && func_bound_stride > 0 && func_neg < 0.f,
                   "func must be int32 [heads or 1][n_func odd][tokens], func_neg negative");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  tl_rab = RabCall{};
-  tl_rab.func = func; tl_rab.fh = func_head_stride; tl_rab.fp = func_bound_stride; tl_rab.nf = (int)n_func; tl_rab.fneg = func_neg;
-  const int rc = HSTU_FN(mi355_hstu_attn_fwd_kv)(q, k, v, out, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride,
-                                        k_head_stride, v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads,
-                                        head_dim, max_seqlen_q, num_contexts, num_targets, target_group_size, causal, alpha,
-                                        scaling_seqlen, kv_cache, page_offsets, page_ids, last_page_lens, page_size, stream);
-  tl_rab = RabCall{};
-  tl_wl = tl_wr = -1;
-  return rc;
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.func = func; c.func_h = func_head_stride; c.func_p = func_bound_stride; c.n_func = (int)n_func; c.func_neg = func_neg;
+  c.kv_cache = kv_cache; c.page_offsets = page_offsets; c.page_ids = page_ids; c.last_page_lens = last_page_lens; c.page_size = page_size;
+  return hstu_forward(c);
 }
 
 int HSTU_FN(mi355_hstu_attn_bwd_func)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
@@ -4505,24 +4473,19 @@ int HSTU_FN(mi355_hstu_attn_bwd_func)(const void* dout, const void* q, const voi
                              int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
                              void* func_workspace, int64_t func_workspace_bytes, void* workspace, int64_t workspace_bytes,
                              hipStream_t stream) {
-  GradStridesDrop drop_unreached_binding;
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen,
+                             max_seqlen, alpha, scaling_seqlen, stream);
   MI355_CHECK_ARG(func != nullptr && n_func >= 1 && (n_func & 1) == 1 && func_bound_stride > 0 && func_neg < 0.f,
                   "func must be int32 [heads or 1][n_func odd][tokens], func_neg negative");
-  int causal = 0;
-  if (const int rc = rab_mask(window_left, window_right, num_contexts, num_targets, &causal)) return rc;
-  tl_rab = RabCall{};
-  tl_rab.func = func; tl_rab.fh = func_head_stride; tl_rab.fp = func_bound_stride; tl_rab.nf = (int)n_func; tl_rab.fneg = func_neg;
-  tl_rab.kvis = func_workspace; tl_rab.kvis_bytes = func_workspace_bytes;
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  c.func = func; c.func_h = func_head_stride; c.func_p = func_bound_stride; c.n_func = (int)n_func; c.func_neg = func_neg;
+  c.func_ws = func_workspace; c.func_ws_bytes = func_workspace_bytes;
   // the P / dS exchange (as mi355_hstu_attn_bwd's workspace) serves functions of up to two bands at head dim 256 when the tables
   // above are there (the passes that read the exchange replay the table to know which sub-tiles exist); otherwise: the recomputing passes
-  const bool xch = head_dim == 256 && n_func <= 5 && func_workspace != nullptr && window_skip();
-  const int rc = HSTU_FN(mi355_hstu_attn_bwd)(dout, q, k, v, dq, dk, dv, q_row_stride, k_row_stride, v_row_stride, do_row_stride,
-                                     q_head_stride, k_head_stride, v_head_stride, do_head_stride, cu_seqlens, batch, num_heads,
-                                     head_dim, max_seqlen, num_contexts, num_targets, target_group_size, causal, alpha,
-                                     scaling_seqlen, xch ? workspace : nullptr, xch ? workspace_bytes : 0, stream);
-  tl_rab = RabCall{};
-  tl_wl = tl_wr = -1;
-  return rc;
+  if (head_dim == 256 && n_func <= 5 && func_workspace != nullptr && window_skip()) { c.ws = workspace; c.ws_bytes = workspace_bytes; }
+  return hstu_backward(c);
 }
 
 }  // extern "C"

@@ -1413,3 +1413,40 @@ def test_raw_fbgemm_ops_of_the_fused_layer_match_the_wrapper():
                                                 None, 1, 16, 5, alpha, -1, None, False, None, None, None, None, None, None, None,
                                                 None, None, None, None, None, 0, False)
         assert torch.equal(r[0], gq) and torch.equal(r[1], gk) and torch.equal(r[2], gv)
+
+
+@pytest.mark.parametrize("d,tdt", [(64, torch.bfloat16), (256, torch.bfloat16), (64, torch.float16)], ids=["d64_bf16", "d256_bf16", "d64_fp16"])
+def test_a_masked_raw_op_that_fails_a_shared_check_leaves_nothing_to_the_next_call(d, tdt):
+    """every masked raw op, called with scaling_seqlen = 0: it passes the checks of its own entry point and fails one that all entry
+    points share, with its window / bias / mask functions already in the call.  The plain forward and backward that follow give
+    what they gave before any failed call, bit for bit."""
+    import hstu.hstu_attn_interface as I
+    from mi355_native import NativeError
+
+    rng = np.random.default_rng(11 + d)
+    lengths = np.array([37, 5, 130])
+    off, q, k, v, dout, f = _func_case(rng, lengths, 2, d, tdt)
+    B, N = lengths.size, int(lengths.max())
+    cu = torch.from_numpy(off.astype(np.int32)).to(DEV)
+    func = torch.from_numpy(f).to(DEV)
+    rab = torch.from_numpy(rng.standard_normal((B, 1, N, N)).astype(np.float32)).to(DEV).to(tdt)
+    alpha = 1.0 / d ** 0.5
+
+    def plain():
+        out = I.hstu_varlen_fwd(q, k, v, cu, N, float(N), None, None, 1, True, alpha)
+        return (out, *I.hstu_varlen_bwd(dout, q, k, v, cu, N, float(N), None, None, 1, True, alpha))
+
+    failing = {
+        "fwd_window": lambda: I.hstu_varlen_fwd_window(q, k, v, cu, N, 0.0, 20, 3, alpha),
+        "fwd_rab": lambda: I.hstu_varlen_fwd_rab(q, k, v, cu, N, 0.0, None, None, 1, 20, 3, alpha, rab),
+        "fwd_func": lambda: I.hstu_varlen_fwd_func(q, k, v, cu, None, N, N, 0.0, None, None, 1, 20, 3, alpha, func),
+        "bwd_window": lambda: I.hstu_varlen_bwd_window(dout, q, k, v, cu, N, 0.0, 20, 3, alpha),
+        "bwd_rab": lambda: I.hstu_varlen_bwd_rab(dout, q, k, v, cu, N, 0.0, None, None, 1, 20, 3, alpha, rab, True),
+        "bwd_func": lambda: I.hstu_varlen_bwd_func(dout, q, k, v, cu, N, 0.0, None, None, 1, 20, 3, alpha, func),
+    }
+    want = plain()
+    for name, call in failing.items():
+        with pytest.raises(NativeError, match="scaling_seqlen must be positive"):
+            call()
+        for a_, b_ in zip(want, plain()):
+            assert torch.equal(a_, b_), f"a failed hstu_varlen_{name} changed the next plain call"
