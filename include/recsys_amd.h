@@ -722,6 +722,61 @@ int mi355_hstu_attn_bwd_func_f16(const void* dout, const void* q, const void* k,
                              void* func_workspace, int64_t func_workspace_bytes, void* workspace, int64_t workspace_bytes,
                              hipStream_t stream);
 
+/* Mask functions BESIDE a relative attention bias (hstu_attn_varlen_func(rab=..., func=...); the reference's kernels take the two
+ * together, Has_rab x Is_arbitrary), both read inside the kernels: per key tile the row's rab values are added to q.k, then the
+ * function test adds func_neg where the row does not see the key.  Key tiles no row of a wave reaches are skipped before their rab
+ * row is loaded; no [batch, heads, N, N] mask tensor exists.  With num_contexts the functions narrow the mask except for the history
+ * columns of contextual rows.  Arguments: the mask arguments, the four rab arguments and the five func arguments as in
+ * mi355_hstu_attn_fwd_kv_rab / mi355_hstu_attn_fwd_kv_func, then the paged cache.  cu_seqlens_k NULL = self attention (training);
+ * otherwise delta-q keys and / or the paged cache (rab by absolute positions, func by query token).  Each entry point checks the
+ * window, the causal mask, rab (and drab), func, then what every entry point checks. */
+int mi355_hstu_attn_fwd_kv_rab_func(const void* q, const void* k, const void* v, void* out, int64_t q_row_stride,
+                                    int64_t k_row_stride, int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride,
+                                    int64_t k_head_stride, int64_t v_head_stride, int64_t o_head_stride,
+                                    const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads,
+                                    int64_t head_dim, int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                                    const int32_t* num_targets, int64_t target_group_size, int64_t window_left,
+                                    int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
+                                    int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, const int32_t* func,
+                                    int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
+                                    const void* kv_cache, const int32_t* page_offsets, const int32_t* page_ids,
+                                    const int32_t* last_page_lens, int64_t page_size, hipStream_t stream);
+int mi355_hstu_attn_fwd_kv_rab_func_f16(const void* q, const void* k, const void* v, void* out, int64_t q_row_stride,
+                                    int64_t k_row_stride, int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride,
+                                    int64_t k_head_stride, int64_t v_head_stride, int64_t o_head_stride,
+                                    const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads,
+                                    int64_t head_dim, int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                                    const int32_t* num_targets, int64_t target_group_size, int64_t window_left,
+                                    int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
+                                    int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, const int32_t* func,
+                                    int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
+                                    const void* kv_cache, const int32_t* page_offsets, const int32_t* page_ids,
+                                    const int32_t* last_page_lens, int64_t page_size, hipStream_t stream);
+/* The backward of the self-attention call: the recomputing passes (the key-major dV / dK pass(es) under the per-key-block table of
+ * func_workspace, the query-major dQ pass under the func extents of its rows).  drab (nullable) as in mi355_hstu_attn_bwd_rab: one
+ * [max_seqlen][max_seqlen] matrix per head, zero-filled by the caller; it receives dS wherever the row sees the key and zero where
+ * the functions mask.  func_workspace / func_workspace_bytes as in mi355_hstu_attn_bwd_func (nullable). */
+int mi355_hstu_attn_bwd_rab_func(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                                 int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                                 int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                                 const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                                 const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                                 int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
+                                 int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
+                                 int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, const int32_t* func,
+                                 int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
+                                 void* func_workspace, int64_t func_workspace_bytes, hipStream_t stream);
+int mi355_hstu_attn_bwd_rab_func_f16(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                                 int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                                 int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                                 const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                                 const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                                 int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
+                                 int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
+                                 int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, const int32_t* func,
+                                 int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
+                                 void* func_workspace, int64_t func_workspace_bytes, hipStream_t stream);
+
 /* append_kvcache (torch.ops.paged_kvcache_ops.append_kvcache, examples/commons/ops/cuda_ops/csrc/
  * paged_kvcache_ops_kernel.cu:106-140, call site paged_hstu_infer_layer.py:350-364): new-history token i (i < *nnz_dev,
  * or < max_nnz when max_nnz > 0) of sequence batch_indices[i] is written at position positions[i] of that user's

@@ -442,7 +442,9 @@ __device__ __forceinline__ unsigned tick() {
 #define TACC(i, a, b)
 #endif
 
-template <int D, bool kWin = false, bool kRab = false>   // kWin: local window, kRab: attention bias; variants of their own so that the plain path pays nothing
+// kBoth (with kRab): the bias AND the mask functions of one call -- per tile the row's rab values, then the function test, under the
+// function extents' tile skipping; a flag of its own so that the rab-only / func-only instantiation keeps its instruction stream
+template <int D, bool kWin = false, bool kRab = false, bool kBoth = false>   // kWin: local window, kRab: attention bias; variants of their own so that the plain path pays nothing
 __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
   constexpr int KS = D + 8;    // padded K row (elements)
   // V tile in LDS: transposed [D][VS] by the committing threads (perm + 8-byte stores).  Measured and rejected: a row-major V
@@ -705,7 +707,11 @@ __global__ void __launch_bounds__(256) hstu_fwd_kernel(AttnArgs a) {
       }
     }
     fence_v(acc_s);
-    if constexpr (kRab) {
+    if constexpr (kBoth) {   // (a tile no row of the wave reaches never got here: its rab row is not loaded)
+      const uint16_t* row = qi < s.L ? a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + (int64_t)qi * a.rab_r : nullptr;
+      add_rab_row<2>(acc_s, row, n0, hi, s.L);
+      if (n0 + kBN > wx.f0min) add_func_row<2>(acc_s, a, h, (int64_t)s.start + qloc, qloc < Lq, n0, hi, s.L, (s.has_ctx && qi < s.c) ? s.hlen : 0);
+    } else if constexpr (kRab) {
       if (a.func) {     // (a tile below the smallest prefix of the wave's rows is seen by all of them: nothing to test)
         if (n0 + kBN > wx.f0min) add_func_row<2>(acc_s, a, h, (int64_t)s.start + qloc, qloc < Lq, n0, hi, s.L, (s.has_ctx && qi < s.c) ? s.hlen : 0);
       } else {
@@ -2165,7 +2171,7 @@ __device__ __forceinline__ KvSpan kv_span_dq(const AttnArgs& a, const SeqInfo& s
 // K / V fragments exceed the register file of one wave, so the pass is split: MODE 1 = dV only (S -> P -> dV),
 // MODE 2 = dK only (S, dP -> dS -> dK).  Loop structure as in the forward: register-prefetched tiles, explicit
 // AGPR output accumulators, double-buffered LDS fragment batches, branch-free mask.
-template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
+template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false, bool kBoth = false>
 __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;   // kXP (MODE 2): P is computed as well and left for the dV pass
@@ -2330,6 +2336,41 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
     if (kDK) fence_v(acc_p);
     TICK(t5);
     TACC(4, t4, t5);
+    if constexpr (kBoth) {   // the bias column first, then the function test (a step the table skipped never got here)
+      if (kj < s.L) {
+        const uint16_t* col = a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + kj;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr) {
+            const int qi = p0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+            if (qi < s.L) acc_s[t][rr] += bf16_bits_to_f32(col[(int64_t)qi * a.rab_r]);
+          }
+      }
+      bool func_full = false;   // (as below: every query row of the step sees every key of the block)
+      if (g.func_gext) {
+        const int64_t gi = func_gext_index(s.start, b, i0);
+        if (gi + NT <= 4 * g.func_kvis_h) {
+          int fmin = 0x7fffffff;
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            const int f = g.func_gext[(int64_t)(a.func_h ? h : 0) * 4 * g.func_kvis_h + gi + t].x;
+            fmin = f < fmin ? f : fmin;
+          }
+          func_full = n0 + kBM <= fmin;
+        }
+      }
+      if (kj < s.L && !func_full) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr) {
+            const int qi = p0 + 32 * t + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+            if (qi < s.L && !(s.has_ctx && qi < s.c && kj < s.hlen) &&
+                !func_sees(a.func + (int64_t)h * a.func_h + qr.qstart + (qi - qr.qoff), a.func_p, a.n_func, kj)) acc_s[t][rr] += a.func_neg;
+          }
+      }
+    } else
     if constexpr (kRab) {   // lane = key kj, registers = query rows: rab[qi][kj]
       if (a.func) {         // (the bounds of a query row are the same words for the 32 lanes of a half-wave: one transaction)
         // a step whose query rows all see every key of the block (the block lies below their smallest prefix) needs no test
@@ -2516,7 +2557,7 @@ __global__ void __launch_bounds__(256) hstu_bwd_kv_kernel(BwdAttnArgs g) {
 
 // pass B: one workgroup = 128 queries (32 per wave); loops over key tiles of BK keys -> dQ
 // kDq (delta-q): the workgroup's rows are rows of q at the absolute positions qr.qoff + row; its key tiles are clipped from those
-template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false>
+template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false, bool kBoth = false>
 __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
   const AttnArgs& a = g.f;
   constexpr int RS = D + 8, NT = BK / 32;
@@ -2640,7 +2681,11 @@ __global__ void __launch_bounds__(256) hstu_bwd_q_kernel(BwdAttnArgs g) {
     }
     fence_v(acc_s);
     fence_v(acc_p);
-    if constexpr (kRab) {
+    if constexpr (kBoth) {
+      const uint16_t* row = qi < qr.Lq ? a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + (int64_t)pi * a.rab_r : nullptr;
+      add_rab_row<NT>(acc_s, row, n0, hi, s.L);
+      if (n0 + BK > wx.f0min) add_func_row<NT>(acc_s, a, h, (int64_t)qr.qstart + qi, qi < qr.Lq, n0, hi, s.L, (s.has_ctx && pi < s.c) ? s.hlen : 0);
+    } else if constexpr (kRab) {
       if (a.func) { if (n0 + BK > wx.f0min) add_func_row<NT>(acc_s, a, h, (int64_t)qr.qstart + qi, qi < qr.Lq, n0, hi, s.L, (s.has_ctx && pi < s.c) ? s.hlen : 0); }
       else {
       const uint16_t* row = qi < qr.Lq ? a.rab + (int64_t)b * a.rab_b + (int64_t)h * a.rab_h + (int64_t)pi * a.rab_r : nullptr;
@@ -3693,17 +3738,17 @@ static int launched(int failed) {
   return MI355_OK;
 }
 
-template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false>
+template <int D, int BQ, int MODE, bool kPre, bool kXP = false, bool kRab = false, bool kDq = false, bool kBoth = false>
 static int launch_bwd_kv(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   constexpr bool kDV = MODE != 2, kDK = MODE != 1;
   const size_t timg = (size_t)BQ * TrStride<D>::value;
   const size_t smem = (size_t)(BQ * (D + 8) + (kDK ? BQ * (D + 8) + timg : 0) + (kDV ? timg : 0)) * sizeof(uint16_t);
-  return launch<hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq>>(grid, dim3(256), smem, stream, g);
+  return launch<hstu_bwd_kv_kernel<D, BQ, MODE, kPre, kXP, kRab, kDq, kBoth>>(grid, dim3(256), smem, stream, g);
 }
-template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false>
+template <int D, int BK, bool kPre, bool kRab = false, bool kDq = false, bool kBoth = false>
 static int launch_bwd_q(const BwdAttnArgs& g, dim3 grid, hipStream_t stream) {
   const size_t smem_q = (size_t)(2 * BK * (D + 8) + BK * TrStride<D>::value) * sizeof(uint16_t);
-  return launch<hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq>>(grid, dim3(256), smem_q, stream, g);
+  return launch<hstu_bwd_q_kernel<D, BK, kPre, kRab, kDq, kBoth>>(grid, dim3(256), smem_q, stream, g);
 }
 
 template <int D>   // (head dim 128; 256 takes launch_bwd_x8)
@@ -3738,6 +3783,17 @@ static int launch_bwd(BwdAttnArgs g, int B, int max_seqlen, hipStream_t stream) 
       g.bq_kv = 32;
       return launch_bwd_pc_x8<true>(g, grid, B, max_seqlen, stream);
     }
+  }
+  if (g.f.rab && g.f.func) {   // both in one call: the same passes, the instantiations that read the two operands
+    g.ds_ws = g.p_ws = nullptr;
+    g.bq_kv = 64;
+    if constexpr (D >= 128)
+      return launched(launch_bwd_kv<D, 64, 1, false, false, true, false, true>(g, grid, stream) ||
+                      launch_bwd_kv<D, 32, 2, false, false, true, false, true>(g, grid, stream) ||
+                      launch_bwd_q<D, D >= 256 ? 32 : 64, false, true, false, true>(g, grid, stream));
+    else
+      return launched(launch_bwd_kv<D, 64, 0, false, false, true, false, true>(g, grid, stream) ||
+                      launch_bwd_q<D, 64, false, true, false, true>(g, grid, stream));
   }
   if (g.f.rab || g.f.func) {   // attention bias / mask functions: the recomputing passes (S needs the bias in every pass), dS doubles as d rab
     g.ds_ws = g.p_ws = nullptr;
@@ -3832,6 +3888,7 @@ static int launch_fwd(const AttnArgs& a, int B, int max_seqlen, hipStream_t stre
   // are handed out first and the light ones fill in behind them.  With the rank in x (per-sequence order 8,6,4,2 key
   // tiles at L = 512) the CUs freed first drew heavy blocks again and the slowest CU did 16 tiles where 10 is the mean.
   dim3 grid(a.H, B, (max_seqlen + kBM - 1) / kBM);
+  if (a.rab && a.func) return launched(launch<hstu_fwd_kernel<D, true, true, true>>(grid, dim3(256), smem, stream, a));
   if (a.rab || a.func) return launched(launch<hstu_fwd_kernel<D, true, true>>(grid, dim3(256), smem, stream, a));
   if (a.wl >= 0 || a.wr >= 0) return launched(launch<hstu_fwd_kernel<D, true>>(grid, dim3(256), smem, stream, a));
   return launched(launch<hstu_fwd_kernel<D, false>>(grid, dim3(256), smem, stream, a));
@@ -4486,6 +4543,69 @@ int HSTU_FN(mi355_hstu_attn_bwd_func)(const void* dout, const void* q, const voi
   // above are there (the passes that read the exchange replay the table to know which sub-tiles exist); otherwise: the recomputing passes
   if (head_dim == 256 && n_func <= 5 && func_workspace != nullptr && window_skip()) { c.ws = workspace; c.ws_bytes = workspace_bytes; }
   return hstu_backward(c);
+}
+
+// Mask functions BESIDE a relative attention bias, both read inside the kernels (the reference instantiates Has_rab x Is_arbitrary,
+// hopper/hstu_api.cpp; its Ampere kernels read both in one loop): per tile the row's rab values are added to q.k, then the function
+// test adds func_neg where the row does not see the key; key tiles no row of a wave reaches are skipped in front of the rab load
+// (the func extents, as mi355_hstu_attn_fwd_kv_func).  With contextual rows the functions narrow the mask except for the history
+// columns of those rows.  Arguments: those of mi355_hstu_attn_fwd_kv_rab with the five func arguments behind the bias.  Forward:
+// training keys (cu_seqlens_k NULL), delta-q keys and the paged cache.  Its own checks in front of the shared ones: window, causal
+// mask, rab, func.
+int HSTU_FN(mi355_hstu_attn_fwd_kv_rab_func)(const void* q, const void* k, const void* v, void* out, int64_t q_row_stride,
+                                    int64_t k_row_stride, int64_t v_row_stride, int64_t o_row_stride, int64_t q_head_stride,
+                                    int64_t k_head_stride, int64_t v_head_stride, int64_t o_head_stride, const int32_t* cu_seqlens_q,
+                                    const int32_t* cu_seqlens_k, int64_t batch, int64_t num_heads, int64_t head_dim,
+                                    int64_t max_seqlen_q, int64_t max_seqlen_k, const int32_t* num_contexts,
+                                    const int32_t* num_targets, int64_t target_group_size, int64_t window_left, int64_t window_right,
+                                    float alpha, float scaling_seqlen, const void* rab, int64_t rab_batch_stride,
+                                    int64_t rab_head_stride, int64_t rab_row_stride, const int32_t* func, int64_t func_head_stride,
+                                    int64_t func_bound_stride, int64_t n_func, float func_neg, const void* kv_cache,
+                                    const int32_t* page_offsets, const int32_t* page_ids, const int32_t* last_page_lens,
+                                    int64_t page_size, hipStream_t stream) {
+  HstuCall c = forward_call(out, q, k, v, q_row_stride, k_row_stride, v_row_stride, o_row_stride, q_head_stride, k_head_stride,
+                            v_head_stride, o_head_stride, cu_seqlens_q, cu_seqlens_k, batch, num_heads, head_dim, max_seqlen_q,
+                            max_seqlen_k, alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen_k, "rab must be [batch][heads or 1][max_seqlen_k][max_seqlen_k]");
+  MI355_CHECK_ARG(func != nullptr && n_func >= 1 && (n_func & 1) == 1 && func_bound_stride > 0 && func_neg < 0.f,
+                  "func must be int32 [heads or 1][n_func odd][tokens], func_neg negative");
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  c.func = func; c.func_h = func_head_stride; c.func_p = func_bound_stride; c.n_func = (int)n_func; c.func_neg = func_neg;
+  c.kv_cache = kv_cache; c.page_offsets = page_offsets; c.page_ids = page_ids; c.last_page_lens = last_page_lens; c.page_size = page_size;
+  return hstu_forward(c);
+}
+
+// ... and its backward: self attention over contiguous keys, the recomputing passes (S needs both operands in every pass).  drab as
+// mi355_hstu_attn_bwd_rab: one [max_seqlen][max_seqlen] matrix per head, zero-filled by the caller; it receives dS wherever the row
+// sees the key and zero where the functions mask (tiles the passes skip stay as the caller filled them).  func_workspace as
+// mi355_hstu_attn_bwd_func (the key-block table of the key-major passes).
+int HSTU_FN(mi355_hstu_attn_bwd_rab_func)(const void* dout, const void* q, const void* k, const void* v, void* dq, void* dk, void* dv,
+                                 int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride, int64_t do_row_stride,
+                                 int64_t q_head_stride, int64_t k_head_stride, int64_t v_head_stride, int64_t do_head_stride,
+                                 const int32_t* cu_seqlens, int64_t batch, int64_t num_heads, int64_t head_dim, int64_t max_seqlen,
+                                 const int32_t* num_contexts, const int32_t* num_targets, int64_t target_group_size,
+                                 int64_t window_left, int64_t window_right, float alpha, float scaling_seqlen, const void* rab,
+                                 int64_t rab_batch_stride, int64_t rab_head_stride, int64_t rab_row_stride, void* drab,
+                                 int64_t drab_batch_stride, int64_t drab_head_stride, int64_t drab_row_stride, const int32_t* func,
+                                 int64_t func_head_stride, int64_t func_bound_stride, int64_t n_func, float func_neg,
+                                 void* func_workspace, int64_t func_workspace_bytes, hipStream_t stream) {
+  HstuCall c = backward_call(dout, dq, dk, dv, q, k, v, q_row_stride, k_row_stride, v_row_stride, do_row_stride, q_head_stride,
+                             k_head_stride, v_head_stride, do_head_stride, cu_seqlens, nullptr, batch, num_heads, head_dim, max_seqlen,
+                             max_seqlen, alpha, scaling_seqlen, stream);
+  c.num_contexts = num_contexts; c.num_targets = num_targets; c.group = target_group_size;
+  if (const int rc = set_mask(c, window_left, window_right)) return rc;
+  MI355_CHECK_ARG(rab != nullptr && rab_row_stride >= max_seqlen, "rab must be [batch][heads or 1][max_seqlen][max_seqlen]");
+  MI355_CHECK_ARG(drab == nullptr || (drab_row_stride >= max_seqlen && drab_head_stride > 0),
+                  "drab must hold one [max_seqlen][max_seqlen] matrix per head");
+  MI355_CHECK_ARG(func != nullptr && n_func >= 1 && (n_func & 1) == 1 && func_bound_stride > 0 && func_neg < 0.f,
+                  "func must be int32 [heads or 1][n_func odd][tokens], func_neg negative");
+  c.rab = rab; c.rab_b = rab_batch_stride; c.rab_h = rab_head_stride; c.rab_r = rab_row_stride;
+  c.drab = drab; c.drab_b = drab_batch_stride; c.drab_h = drab_head_stride; c.drab_r = drab_row_stride;
+  c.func = func; c.func_h = func_head_stride; c.func_p = func_bound_stride; c.n_func = (int)n_func; c.func_neg = func_neg;
+  c.func_ws = func_workspace; c.func_ws_bytes = func_workspace_bytes;
+  return hstu_backward(c);   // (no exchange with a bias: the recomputing passes)
 }
 
 }  // extern "C"

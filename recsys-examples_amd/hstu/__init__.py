@@ -9,7 +9,7 @@ from .hstu_attn_interface import (HstuAttnVarlenFunc, HstuAttnWindowFunc, append
                                   hstu_varlen_bwd, hstu_varlen_bwd_window, hstu_varlen_fwd, hstu_varlen_fwd_kv,
                                   hstu_varlen_fwd_window, HstuAttnRabFunc, hstu_varlen_fwd_rab, hstu_varlen_bwd_rab,
                                   HstuAttnDeltaQFunc, hstu_varlen_bwd_kv, HstuAttnQKVPackedFunc, hstu_attn_qkvpacked_func,
-                                  hstu_varlen_bwd_func)
+                                  hstu_varlen_bwd_func, HstuAttnRabFuncFunc, hstu_varlen_fwd_rab_func, hstu_varlen_bwd_rab_func)
 from .hstu_fp8 import (HstuAttnFp8Func, get_bm_and_bn_block_size_bwd, get_bm_and_bn_block_size_fwd,  # noqa: F401
                        quantize_for_backward, quantize_for_block_scale, quantize_for_head_batch_tensor,
                        quantize_for_two_directions, varlen_bwd, varlen_fwd)

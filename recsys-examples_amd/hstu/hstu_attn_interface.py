@@ -11,8 +11,9 @@ call -- plain, window and rab masks, drab included (HstuAttnDeltaQFunc over mi35
 same offset) --; the paged cache, `func` over delta-q keys and FP8 are forward only.
 Arbitrary mask functions (`func`, hstu_api.cpp:170-180) are read INSIDE the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func: no mask
 tensor exists), forward and backward, with any other mask -- contextual rows keep their view of the history, as in the
-reference's kernels (hstu_fwd.h:519-524) --, over delta-q / paged keys too.  Next to a relative bias they are added to it as a
-0 / -1e9 bias (func_mask_bias: O(batch max_seqlen_k^2) memory, like the bias itself).
+reference's kernels (hstu_fwd.h:519-524) --, over delta-q / paged keys too, and beside a relative bias
+(mi355_hstu_attn_{fwd_kv,bwd}_rab_func: the kernels read both).  MI355_HSTU_FUNC_DENSE=1 keeps the dense statement as the A/B
+switch: a 0 / -1e9 bias (func_mask_bias: O(batch max_seqlen_k^2) memory) through the biased kernels.
 Not supported (raise): seqused_* (no caller of the reference passes them, and its kernels take none).  The raw ops of the fused layer
 (`torch.ops.fbgemm.hstu_varlen_{fwd,bwd}_{80,90}`) are registered by `hstu.hstu_ops_gpu`.
 """
@@ -64,6 +65,12 @@ N.register_signatures({
     "mi355_hstu_attn_bwd_func": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p,
                                  c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
                                  c_f, c_p, c_i64, c_p, c_i64, c_p],
+    "mi355_hstu_attn_fwd_kv_rab_func": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64,
+                                        c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
+                                        c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_attn_bwd_rab_func": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p,
+                                     c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_i64, c_i64, c_i64,
+                                     c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_i64, c_p],
     "mi355_append_kvcache": [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p,
                              c_i64, c_i64, c_p],
 }, {"mi355_hstu_attn_bwd_workspace_bytes": c_i64, "mi355_hstu_attn_bwd_ds_bytes": c_i64,
@@ -73,7 +80,7 @@ N.register_signatures({
 # the fp16-operand twins of the type-specific entry points (same argument lists)
 _TYPED = ("mi355_hstu_attn_bwd_kv", "mi355_hstu_attn_fwd_hint_tokens", "mi355_hstu_attn_fwd", "mi355_hstu_attn_fwd_kv", "mi355_hstu_attn_fwd_kv_window", "mi355_hstu_attn_fwd_kv_rab", "mi355_hstu_attn_bwd", "mi355_hstu_attn_fwd_window",
           "mi355_hstu_attn_bwd_window", "mi355_hstu_attn_fwd_rab", "mi355_hstu_attn_bwd_rab", "mi355_hstu_attn_fwd_kv_func",
-          "mi355_hstu_attn_bwd_func")
+          "mi355_hstu_attn_bwd_func", "mi355_hstu_attn_fwd_kv_rab_func", "mi355_hstu_attn_bwd_rab_func")
 N.register_signatures({n + "_f16": N.signature_of(n) for n in _TYPED})
 
 
@@ -565,6 +572,83 @@ class HstuAttnFuncFunc(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
 
 
+def _func_workspace(func, q, B):
+    """room for the key-block table the backward fills in front of its key-major passes (72 bytes per key block and function set)"""
+    return torch.empty((func.shape[0] if func.shape[0] > 1 else 1) * (q.shape[0] // 128 + B + 1) * 18, dtype=torch.int32, device=q.device)
+
+
+def hstu_varlen_fwd_rab_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scaling_seqlen, num_contexts, num_targets,
+                             target_group_size, wl, wr, alpha, rab, func, kv_cache=None, page_offsets=None, page_ids=None,
+                             last_page_lens=None):
+    """Raw forward with mask functions beside a relative bias, both read inside the kernel (mi355_hstu_attn_fwd_kv_rab_func): no
+    dense mask bias, no second bias tensor.  cu_seqlens_k None = the keys are the queries' tokens (training); otherwise delta-q
+    keys and / or the paged cache (rab over absolute positions, func by query token)."""
+    T, H, D = q.shape
+    out = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
+    B = cu_seqlens_q.numel() - 1
+    page_size = kv_cache.size(2) if kv_cache is not None else 0
+    rb, rh, rr = _rab_strides(rab, H)
+    check(_fn("mi355_hstu_attn_fwd_kv_rab_func", q)(ptr(q), ptr(k), ptr(v), ptr(out), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
+                                                    q.stride(1), k.stride(1), v.stride(1), out.stride(1), ptr(cu_seqlens_q),
+                                                    ptr(cu_seqlens_k), B, H, D, int(max_seqlen_q), int(max_seqlen_k),
+                                                    ptr(num_contexts), ptr(num_targets), int(target_group_size), int(wl), int(wr),
+                                                    c_f(alpha), c_f(float(scaling_seqlen)), ptr(rab), rb, rh, rr, ptr(func),
+                                                    func.stride(0) if func.shape[0] > 1 else 0, func.stride(1), func.shape[1],
+                                                    c_f(_func_neg_value(q.dtype)), ptr(kv_cache), ptr(page_offsets), ptr(page_ids),
+                                                    ptr(last_page_lens), page_size, stream()), "hstu_attn_fwd_kv_rab_func")
+    return out
+
+
+def hstu_varlen_bwd_rab_func(dout, q, k, v, cu_seqlens, max_seqlen, scaling_seqlen, num_contexts, num_targets, target_group_size,
+                             wl, wr, alpha, rab, has_drab, func, *, dq=None, dk=None, dv=None):
+    """Raw backward with mask functions beside a relative bias: (dq, dk, dv, drab or None).  drab has the shape of rab, dS where the
+    row sees the key and zero where the functions mask; with one shared bias head it is the sum over the heads, formed in fp32 from
+    per-head matrices (as hstu_varlen_bwd_rab) -- a per-head function over one bias head included."""
+    T, H, D = q.shape
+    dout = dout.contiguous() if dout.stride(-1) != 1 else dout
+    go = _GradOut(q, k, dq, dk, dv)
+    dq, dk, dv = go.to
+    B = cu_seqlens.numel() - 1
+    N = rab.shape[-1]
+    rb, rh, rr = _rab_strides(rab, H)
+    drab = torch.zeros((B, H, N, N), dtype=q.dtype, device=q.device) if has_drab else None
+    ds = (drab.stride(0), drab.stride(1), drab.stride(2)) if has_drab else (0, 0, 0)
+    fws = _func_workspace(func, q, B)
+    go.bind()
+    check(_fn("mi355_hstu_attn_bwd_rab_func", q)(ptr(dout), ptr(q), ptr(k), ptr(v), ptr(dq), ptr(dk), ptr(dv), q.stride(0), k.stride(0),
+                                                 v.stride(0), dout.stride(0), q.stride(1), k.stride(1), v.stride(1), dout.stride(1),
+                                                 ptr(cu_seqlens), B, H, D, int(max_seqlen), ptr(num_contexts), ptr(num_targets),
+                                                 int(target_group_size), int(wl), int(wr), c_f(alpha), c_f(float(scaling_seqlen)),
+                                                 ptr(rab), rb, rh, rr, ptr(drab), ds[0], ds[1], ds[2], ptr(func),
+                                                 func.stride(0) if func.shape[0] > 1 else 0, func.stride(1), func.shape[1],
+                                                 c_f(_func_neg_value(q.dtype)), ptr(fws), fws.numel() * 4, stream()),
+          "hstu_attn_bwd_rab_func")
+    if has_drab and rab.shape[1] == 1 and H > 1:
+        drab = drab.float().sum(1, keepdim=True).to(q.dtype)
+    return (*go.result(), drab)
+
+
+class HstuAttnRabFuncFunc(torch.autograd.Function):
+    """attention under mask functions beside a relative bias, both read inside the kernels; rab receives a gradient when has_drab"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rab, func, cu_seqlens, max_seqlen, scaling_seqlen, num_contexts, num_targets, target_group_size, wl,
+                wr, alpha, has_drab):
+        out = hstu_varlen_fwd_rab_func(q, k, v, cu_seqlens, None, max_seqlen, max_seqlen, scaling_seqlen, num_contexts, num_targets,
+                                       target_group_size, wl, wr, alpha, rab, func)
+        ctx.save_for_backward(q, k, v, rab, func, cu_seqlens, num_contexts, num_targets)
+        ctx.meta = (max_seqlen, scaling_seqlen, target_group_size, wl, wr, alpha, has_drab)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, rab, func, cu, nc, nt = ctx.saved_tensors
+        max_seqlen, scaling, g, wl, wr, alpha, has_drab = ctx.meta
+        dq, dk, dv, drab = hstu_varlen_bwd_rab_func(dout, q, k, v, cu, max_seqlen, scaling, nc, nt, g, wl, wr, alpha, rab, has_drab,
+                                                    func, **_into(ctx))
+        return dq, dk, dv, drab, None, None, None, None, None, None, None, None, None, None, None
+
+
 class HstuAttnRabFunc(torch.autograd.Function):
     """attention with a relative bias; rab receives a gradient when has_drab (hstu_attn_interface.py:23-183 of the reference)"""
 
@@ -712,10 +796,26 @@ def _attn_dispatch(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_q, seqused_k, ma
                                             page_offsets, page_ids, last_page_lens)
             return _self_attention(HstuAttnFuncFunc, qkv, q, k, v, func, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen, num_contexts, num_targets,
                                           int(target_group_size), wl, wr, float(alpha))
+    if func is not None and not _FUNC_DENSE:
+        # ... beside a relative bias: both are read inside the kernels (mi355_hstu_attn_{fwd_kv,bwd}_rab_func), under the same
+        # tile skipping and with the same exemption for the history columns of contextual rows
+        _check_func(func, q)
+        if rab.shape[-1] != int(max_seqlen_k):
+            raise RuntimeError("rab must be (batch, nheads or 1, max_seqlen_k, max_seqlen_k)")
+        if not same:   # inference (delta-q keys and / or the paged cache): forward only
+            if has_drab or (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or rab.requires_grad)):
+                raise NotImplementedError("func over delta-q keys or a paged KV cache is forward only (the delta-q backward "
+                                          "takes the plain, window and rab masks)")
+            return hstu_varlen_fwd_rab_func(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), scaling_seqlen,
+                                            num_contexts, num_targets, int(target_group_size), wl, wr, float(alpha), rab, func,
+                                            kv_cache, page_offsets, page_ids, last_page_lens)
+        return _self_attention(HstuAttnRabFuncFunc, qkv, q, k, v, rab, func, cu_seqlens_q, int(max_seqlen_k), scaling_seqlen,
+                               num_contexts, num_targets, int(target_group_size), wl, wr, float(alpha), bool(has_drab))
     if func is not None:
-        # with a relative bias as well (or MI355_HSTU_FUNC_DENSE=1): a bias of 0 / -1e9 through the biased kernels (func_mask_bias)
+        # MI355_HSTU_FUNC_DENSE=1, the A/B switch: a bias of 0 / -1e9 through the biased kernels (func_mask_bias)
         if num_contexts is not None:
-            raise NotImplementedError("func together with num_contexts needs the in-kernel mask functions (no rab)")
+            raise NotImplementedError("MI355_HSTU_FUNC_DENSE=1: a dense bias cannot exempt the history columns of contextual rows "
+                                      "(func together with num_contexts needs the in-kernel mask functions)")
         _check_func(func, q)
         fb = func_mask_bias(func, cu_seqlens_q, cu_seqlens_k, max_seqlen_k, q.dtype)
         if rab is not None and rab.shape[-1] != int(max_seqlen_k):

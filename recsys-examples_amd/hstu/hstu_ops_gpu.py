@@ -6,7 +6,8 @@ The reference's fused HSTU layer does not go through `hstu_attn_varlen_func`: it
 Importing this module (the example does: `import hstu.hstu_ops_gpu`, fused_hstu_op.py:19-20) defines all four ops with the
 positional order of those call sites, backed by the gfx950 kernels, plus Meta kernels for export.  Arguments this build has
 no kernel for (seqused, fp8 quantisation) must be None / default; the ops raise otherwise.  `func` (arbitrary mask functions)
-is read inside the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func); next to a relative bias it is added to it as a 0 / -1e9 bias
+is read inside the kernels (mi355_hstu_attn_{fwd_kv,bwd}_func), next to a relative bias as well
+(mi355_hstu_attn_{fwd_kv,bwd}_rab_func); MI355_HSTU_FUNC_DENSE=1 adds it to the bias as a 0 / -1e9 bias instead
 (hstu_attn_interface.func_mask_bias).
 `window_size_left / right` with a finite side run the local-window kernels, `rab` / `has_drab` the bias kernels.
 These raw ops stay self-attention only (cu_seqlens_q == cu_seqlens_k): the fused layer never calls them otherwise.  Delta-q calls,
@@ -14,8 +15,9 @@ forward and backward, go through `hstu_attn_varlen_func` / `hstu.hstu_varlen_bwd
 import torch
 
 from .hstu_fp8 import _FP8_TYPES
+from . import hstu_attn_interface as _hi
 from .hstu_attn_interface import (_check_func, func_mask_bias, hstu_varlen_bwd_func, hstu_varlen_fwd_func, hstu_varlen_bwd, hstu_varlen_bwd_rab, hstu_varlen_bwd_window, hstu_varlen_fwd,
-                                  hstu_varlen_fwd_rab, hstu_varlen_fwd_window)
+                                  hstu_varlen_fwd_rab, hstu_varlen_fwd_window, hstu_varlen_bwd_rab_func, hstu_varlen_fwd_rab_func)
 
 _T = "Tensor"
 _O = "Tensor?"
@@ -33,8 +35,6 @@ def _check(q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, wl, wr, rab,
            num_contexts=None, num_targets=None):
     if seqused_q is not None or seqused_k is not None:
         raise NotImplementedError("seqused_q / seqused_k are not supported")
-    if func is not None and num_contexts is not None and rab is not None:
-        raise NotImplementedError("func together with num_contexts needs the in-kernel mask functions (no rab)")
     if rab is not None and (rab.dim() != 4 or rab.shape[1] not in (1, q.shape[1]) or rab.shape[-1] != max_k or rab.stride(-1) != 1):
         raise RuntimeError("rab must be (batch, nheads or 1, max_seqlen_k, max_seqlen_k) with a contiguous last dimension")
     if quant_mode not in (-1, None) or any(e is not None for e in extra):
@@ -67,7 +67,15 @@ def _fwd(q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, scaling_seqlen
         _check_func(func, q)
         return hstu_varlen_fwd_func(q, k, v, cu_q, None, int(max_q), int(max_k), scaling_seqlen, num_contexts, num_targets,
                                     int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha), func), None
-    if func is not None:   # ... next to a relative bias: a 0 / -1e9 bias added to it (hstu_attn_interface.func_mask_bias)
+    if func is not None and not _hi._FUNC_DENSE:   # ... next to a relative bias: both read inside the kernel
+        _check_func(func, q)
+        out = hstu_varlen_fwd_rab_func(q, k, v, cu_q, None, int(max_q), int(max_k), scaling_seqlen, num_contexts, num_targets,
+                                       int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha), rab, func)
+        return out, rab
+    if func is not None:   # MI355_HSTU_FUNC_DENSE=1: a 0 / -1e9 bias added to it (hstu_attn_interface.func_mask_bias)
+        if num_contexts is not None:
+            raise NotImplementedError("MI355_HSTU_FUNC_DENSE=1: a dense bias cannot exempt the history columns of contextual rows "
+                                      "(func together with num_contexts needs the in-kernel mask functions)")
         fb = func_mask_bias(func, cu_q, cu_k, int(max_k), q.dtype)
         out = hstu_varlen_fwd_rab(q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets, int(target_group_size),
                                   max(int(wl), -1), max(int(wr), -1), float(alpha), fb if rab is None else (rab + fb).clamp_(min=torch.finfo(q.dtype).min))
@@ -96,7 +104,15 @@ def _bwd(dout, q, k, v, cu_q, cu_k, seqused_q, seqused_k, max_q, max_k, scaling_
         _check_func(func, q)
         g = hstu_varlen_bwd_func(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets, int(target_group_size),
                                  max(int(wl), -1), max(int(wr), -1), float(alpha), func, **into)
+    elif func is not None and not _hi._FUNC_DENSE:
+        _check_func(func, q)
+        *g, drab = hstu_varlen_bwd_rab_func(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets,
+                                            int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha), rab,
+                                            bool(has_drab), func, **into)
     elif func is not None:
+        if num_contexts is not None:
+            raise NotImplementedError("MI355_HSTU_FUNC_DENSE=1: a dense bias cannot exempt the history columns of contextual rows "
+                                      "(func together with num_contexts needs the in-kernel mask functions)")
         fb = func_mask_bias(func, cu_q, cu_k, int(max_k), q.dtype)
         *g, drab = hstu_varlen_bwd_rab(dout, q, k, v, cu_q, int(max_k), scaling_seqlen, num_contexts, num_targets,
                                        int(target_group_size), max(int(wl), -1), max(int(wr), -1), float(alpha),
