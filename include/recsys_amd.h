@@ -1098,6 +1098,57 @@ int mi355_hstu_index_rows_sum(const void* d_out, int64_t d_out_stride, int64_t r
                               int64_t table_stride, int64_t K, int table_dtype, void* workspace, int64_t workspace_bytes,
                               hipStream_t stream);
 
+/* ---- HSTU layer norms (csrc/norm_ops.hip) ----
+ * Reference paths below are examples/hstu/ops/triton_ops/, Triton kernels there.  Rows are [rows, D], D in 1 .. 8192, last
+ * dimension contiguous; every row tensor has its own row stride in ELEMENTS.  Rows are fp32 / bf16 / fp16 (`dtype`); weight and
+ * bias [D] are contiguous, fp32 or of the row dtype (`weight_dtype`); mean and rstd are fp32 [rows].  All arithmetic is fp32 and
+ * every stored value is rounded once.  No host sync, no allocation, capturable.  Determinism: no atomics; dweight / dbias are
+ * fp32 sums over the rows in an order fixed by (rows, D), so every output is bitwise reproducible from call to call.
+ *
+ * Dropout (ln_mul_dropout): NOT Triton's tl.rand stream.  Element (row, col) of mask `which` (0 / 1 / 2 for the u / x / t
+ * part of a concat_ux output, 0 otherwise) draws r = word (col & 3) of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ * and counter (row & 0xffffffff, row >> 32, col >> 2, which); it is kept iff r >= floor(dropout_ratio * 2^32) (unsigned), a
+ * kept value is v / (1.0f - (float)dropout_ratio), a dropped one +0.  training == 0 or dropout_ratio == 0: nothing dropped.
+ * The mask is a function of (seed, row, col, which, dropout_ratio) alone, never of the launch geometry. */
+
+/* _layer_norm_fwd / _weighted_layer_norm_fwd (triton_layer_norm.py:313-383).  mean = sum(x) / D, var = sum((x - mean)^2) / D
+ * from the row held on chip, rstd = 1 / sqrt(var + eps), y = (x - mean) rstd w + b; weight == bias == null: w = 1, b = 0.
+ * stats_given != 0: mean / rstd are read as given and nothing is recomputed (COMPUTE_MEAN_AND_RSTD false there); else written. */
+int mi355_hstu_layer_norm_fwd(const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype, const void* weight,
+                              const void* bias, int weight_dtype, float eps, void* y, int64_t y_stride, float* mean, float* rstd,
+                              int stats_given, hipStream_t stream);
+
+/* _layer_norm_bwd_dx / _weighted_layer_norm_bwd_dx + _layer_norm_bwd_dwdb (triton_layer_norm.py:386-481).  xh = (x - mean) rstd,
+ * g = w dy, c1 = sum(xh g) / D, c2 = sum(g) / D, dx = (g - (xh c1 + c2)) rstd + dx_accumulate (may be null; added in fp32 before
+ * the rounding).  weight non-null: dweight = sum_rows dy xh, dbias = sum_rows dy in weight_dtype (zeros for rows == 0), and
+ * workspace (16-byte aligned, mi355_hstu_layer_norm_bwd_workspace_bytes(rows, D), contents irrelevant) is needed. */
+int64_t mi355_hstu_layer_norm_bwd_workspace_bytes(int64_t rows, int64_t D);
+int mi355_hstu_layer_norm_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, int64_t rows, int64_t D,
+                              int dtype, const void* weight, int weight_dtype, const float* mean, const float* rstd,
+                              const void* dx_accumulate, int64_t dx_accumulate_stride, void* dx, int64_t dx_stride, void* dweight,
+                              void* dbias, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* _ln_mul_dropout_fwd (triton_norm_mul_dropout.py:36-127, :361-423).  ln as above, t = ln u; y [rows, D] = drop(t), or with
+ * concat_ux y [rows, 3 D] = [drop0(u) | drop1(x) | drop2(t)].  u is [rows, H, UD] with strides (u_stride0, u_stride1, 1) and
+ * H UD == D (a 2-D u: H = 1, UD = D).  Writes mean and rstd. */
+int mi355_hstu_ln_mul_dropout_fwd(const void* x, int64_t x_stride, const void* u, int64_t u_stride0, int64_t u_stride1, int64_t H,
+                                  int64_t UD, int64_t rows, int64_t D, int dtype, const void* weight, const void* bias,
+                                  int weight_dtype, float eps, double dropout_ratio, int training, uint64_t seed, int concat_ux,
+                                  void* y, int64_t y_stride, float* mean, float* rstd, hipStream_t stream);
+
+/* _ln_mul_dropout_bwd_dx_du + _ln_mul_dropout_bwd_dwdb (triton_norm_mul_dropout.py:130-358, :426-525).  The masks are made again
+ * from the seed.  dy is [rows, D], or [rows, 3 D] = [dy_u | dy_x | dy_t] with concat_ux.  dt = drop2'(dy_t);
+ * du = dt ln (+ drop0'(dy_u)), written with the strides of du (layout of u); dx = the layer-norm backward of g = w dt u
+ * (+ drop1'(dy_x)); dweight = sum_rows dt u xh, dbias = sum_rows dt u.  y non-null: the forward's output is written again,
+ * bit-equal to the forward's.  workspace as above, mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(rows, D). */
+int64_t mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(int64_t rows, int64_t D);
+int mi355_hstu_ln_mul_dropout_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, const void* u,
+                                  int64_t u_stride0, int64_t u_stride1, int64_t H, int64_t UD, int64_t rows, int64_t D, int dtype,
+                                  const void* weight, const void* bias, int weight_dtype, const float* mean, const float* rstd,
+                                  double dropout_ratio, int training, uint64_t seed, int concat_ux, void* dx, int64_t dx_stride,
+                                  void* du, int64_t du_stride0, int64_t du_stride1, void* dweight, void* dbias, void* y,
+                                  int64_t y_stride, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,279 @@
+"""The HSTU layer norms on MI355X: layer norm and layer-norm-mul-dropout, forward and backward, with the names, argument
+order, defaults and return tuples of the reference (examples/hstu/ops/triton_ops/triton_layer_norm.py:313-481, :881-887 and
+triton_norm_mul_dropout.py:361-525, :1148-1182), over the kernels of csrc/norm_ops.hip.
+
+* Binding them is a one-line import change in fused_hstu_op.py, paged_hstu_infer_layer.py and native_hstu_layer.py
+  (INTEGRATION.md §4).  There is no Triton here and no eager fallback: CPU tensors raise.
+* `BLOCK_D` and `num_warps` are the reference's launch parameters: computed by its formulas and returned, ignored when passed
+  back in (the kernels choose their layout from D).
+* x, dy, u, du and dx_accumulate are read and written in place with their strides; only a strided LAST dimension is copied.
+* Dropout is this project's Philox stream (include/recsys_amd.h), not Triton's: a function of (seed, row, col, which, p).
+* dweight / dbias are fp32 sums in a fixed order, bitwise reproducible.  D <= 8192.  group_norm is not implemented.
+"""
+from typing import Optional, Tuple
+
+import torch
+
+import mi355_native as N
+
+__all__ = ["triton_weighted_layer_norm_fwd", "triton_weighted_layer_norm_bwd", "triton_layer_norm_mul_dropout_fwd",
+           "triton_layer_norm_mul_dropout_bwd", "triton_layer_norm", "triton_norm_mul_dropout", "layer_norm", "norm_mul_dropout",
+           "weighted_layer_norm_fwd", "weighted_layer_norm_bwd", "layer_norm_mul_dropout_fwd", "layer_norm_mul_dropout_bwd"]
+
+
+def _next_power_of_2(n: int) -> int:
+    return 1 if n <= 1 else 1 << (int(n) - 1).bit_length()
+
+
+def _launch_params(D: int, element_size: int) -> Tuple[int, int]:
+    """BLOCK_D and num_warps of the reference (triton_layer_norm.py:340-345)"""
+    block_d = min(65536 // element_size, _next_power_of_2(D))
+    if D > block_d:
+        raise RuntimeError("This layer norm doesn't support feature dim >= 64KB.")
+    return block_d, min(max(block_d // 256, 1), 8)
+
+
+def _require_gpu(*ts):
+    dev = None
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise N.NativeError("the layer norms expect GPU tensors (no CPU fallback exists)")
+        if dev is not None and t.device != dev:
+            raise ValueError("all tensors must be on one device")
+        dev = t.device
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """a 2-D tensor whose last dimension is contiguous (any row stride)"""
+    return t if t.stride(1) == 1 or t.size(1) == 1 else t.contiguous()
+
+
+def _stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+
+
+def _u_layout(u: torch.Tensor, D: int, name: str = "u"):
+    """(tensor, stride0, stride1, H, UD) of a [N, D] or [N, H, UD] tensor with a contiguous last dimension"""
+    if u.dim() == 2:
+        u = _rows(u)
+        return u, _stride(u), D, 1, D
+    if u.dim() != 3:
+        raise ValueError(f"{name} must be 2-D or 3-D, got {u.dim()}-D")
+    if u.stride(2) != 1 and u.size(2) != 1:
+        u = u.contiguous()
+    H, UD = u.size(1), u.size(2)
+    s1 = u.stride(1) if H > 1 else UD
+    s0 = u.stride(0) if u.size(0) > 1 else max(u.stride(0), (H - 1) * s1 + UD)
+    return u, s0, s1, H, UD
+
+
+def _check_rows(x, name="x"):
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be 2-D, got {x.dim()}-D")
+    if x.dtype not in N._DT:
+        raise N.NativeError(f"unsupported dtype {x.dtype}")
+
+
+def _check_params(weight, bias, D):
+    if weight.dim() != 1 or bias.dim() != 1 or weight.numel() != D or bias.numel() != D:
+        raise ValueError(f"weight and bias must be 1-D with {D} elements")
+    if weight.dtype != bias.dtype:
+        raise ValueError("weight and bias must share one dtype")
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def triton_weighted_layer_norm_fwd(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+                                   mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None
+                                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int, int]:
+    """y = (x - mean) rstd weight + bias per row (weight None: a plain norm); returns (y, mean, rstd, BLOCK_D, num_warps).
+    When `mean` and `rstd` are both passed they are used as given and nothing is recomputed."""
+    _check_rows(x)
+    _require_gpu(x, weight, bias, mean, rstd)
+    x = _rows(x)
+    rows, D = x.shape
+    learnable = weight is not None
+    if learnable:
+        assert bias is not None
+        _check_params(weight, bias, D)
+        weight, bias = weight.contiguous(), bias.contiguous()
+    y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    given = mean is not None and rstd is not None
+    if mean is None:
+        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    if rstd is None:
+        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    block_d, num_warps = _launch_params(D, x.element_size())
+    N.check(N.lib().mi355_hstu_layer_norm_fwd(
+        N.ptr(x), _stride(x), rows, D, N.dt(x), N.ptr(weight), N.ptr(bias), N.dt(weight) if learnable else N.dt(x), float(eps),
+        N.ptr(y), D, N.ptr(mean), N.ptr(rstd), int(given), N.stream()), "mi355_hstu_layer_norm_fwd")
+    return y, mean, rstd, block_d, num_warps
+
+
+def triton_weighted_layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: Optional[torch.Tensor],
+                                   bias: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor, learnable: bool,
+                                   eps: float, BLOCK_D: int, num_warps: int, dx_accumulate: Optional[torch.Tensor] = None,
+                                   wait_event: Optional[torch.cuda.Event] = None
+                                   ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(dx, dweight, dbias); dx_accumulate, when given, is added to dx in fp32 before the rounding."""
+    _check_rows(x)
+    _require_gpu(dy, x, weight, mean, rstd, dx_accumulate)
+    x, dy = _rows(x), _rows(dy)
+    acc = None if dx_accumulate is None else _rows(dx_accumulate)
+    rows, D = x.shape
+    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    dweight = dbias = ws = None
+    lib = N.lib()
+    if learnable:
+        assert weight is not None and bias is not None
+        weight = weight.contiguous()
+        dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
+        dbias = torch.empty((D,), dtype=weight.dtype, device=x.device)
+        ws = _workspace(lib.mi355_hstu_layer_norm_bwd_workspace_bytes(rows, D), x.device)
+    if wait_event is not None:
+        wait_event.wait(torch.cuda.current_stream())
+    N.check(lib.mi355_hstu_layer_norm_bwd(
+        N.ptr(dy), _stride(dy), N.ptr(x), _stride(x), rows, D, N.dt(x), N.ptr(weight) if learnable else None,
+        N.dt(weight) if learnable else N.dt(x), N.ptr(mean), N.ptr(rstd), N.ptr(acc), 0 if acc is None else _stride(acc),
+        N.ptr(dx), D, N.ptr(dweight), N.ptr(dbias), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream()),
+        "mi355_hstu_layer_norm_bwd")
+    return dx, dweight, dbias
+
+
+def _draw_seed() -> int:
+    # on the CPU generator, as the reference does (triton_norm_mul_dropout.py:397): torch.manual_seed governs it
+    return int(torch.randint(low=0, high=2 ** 62, size=(1,), dtype=torch.int64).item())
+
+
+def triton_layer_norm_mul_dropout_fwd(x: torch.Tensor, u: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                                      dropout_ratio: float, training: bool, concat_ux: bool = False, seed: Optional[int] = None
+                                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int, int, int]:
+    """y = dropout(layer_norm(x) * u), or [dropout(u) | dropout(x) | dropout(ln * u)] with concat_ux;
+    returns (y, mean, rstd, BLOCK_D, num_warps, seed)."""
+    _check_rows(x)
+    _require_gpu(x, u, weight, bias)
+    x = _rows(x)
+    rows, D = x.shape
+    _check_params(weight, bias, D)
+    weight, bias = weight.contiguous(), bias.contiguous()
+    u, us0, us1, H, UD = _u_layout(u, D)
+    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    if rows == 0:
+        return y, mean, rstd, 0, 0, 0
+    block_d, num_warps = _launch_params(D, x.element_size())
+    if seed is None:
+        seed = _draw_seed()
+    N.check(N.lib().mi355_hstu_ln_mul_dropout_fwd(
+        N.ptr(x), _stride(x), N.ptr(u), us0, us1, H, UD, rows, D, N.dt(x), N.ptr(weight), N.ptr(bias), N.dt(weight), float(eps),
+        float(dropout_ratio), int(bool(training)), int(seed), int(bool(concat_ux)), N.ptr(y), y.size(1), N.ptr(mean), N.ptr(rstd),
+        N.stream()), "mi355_hstu_ln_mul_dropout_fwd")
+    return y, mean, rstd, block_d, num_warps, seed
+
+
+def triton_layer_norm_mul_dropout_bwd(dy: torch.Tensor, x: torch.Tensor, u: torch.Tensor, weight: torch.Tensor,
+                                      bias: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, BLOCK_D: int, num_warps: int,
+                                      eps: float, training: bool, dropout_ratio: float, seed: Optional[int] = None,
+                                      concat_ux: bool = False, compute_y: bool = False,
+                                      wait_event: Optional[torch.cuda.Event] = None, du: Optional[torch.Tensor] = None
+                                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """(dx, du, dweight, dbias, y); `du`, when passed, is written in place with its own strides; y (compute_y) is the
+    forward's output again, bit-equal."""
+    _check_rows(x)
+    _require_gpu(dy, x, u, weight, bias, mean, rstd, du)
+    x, dy = _rows(x), _rows(dy)
+    rows, D = x.shape
+    _check_params(weight, bias, D)
+    weight, bias = weight.contiguous(), bias.contiguous()
+    u, us0, us1, H, UD = _u_layout(u, D)
+    if du is None:
+        du = torch.empty_like(u)
+    if du.shape != u.shape or (du.stride(-1) != 1 and du.size(-1) != 1):
+        raise ValueError("du must have the shape of u and a contiguous last dimension")
+    _, ds0, ds1, _, _ = _u_layout(du, D, "du")
+    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device) if compute_y else None
+    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
+    dbias = torch.empty((D,), dtype=weight.dtype, device=x.device)
+    lib = N.lib()
+    ws = _workspace(lib.mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(rows, D), x.device)
+    if wait_event is not None:
+        wait_event.wait(torch.cuda.current_stream())
+    N.check(lib.mi355_hstu_ln_mul_dropout_bwd(
+        N.ptr(dy), _stride(dy), N.ptr(x), _stride(x), N.ptr(u), us0, us1, H, UD, rows, D, N.dt(x), N.ptr(weight), N.ptr(bias),
+        N.dt(weight), N.ptr(mean), N.ptr(rstd), float(dropout_ratio), int(bool(training)), int(seed or 0), int(bool(concat_ux)),
+        N.ptr(dx), D, N.ptr(du), ds0, ds1, N.ptr(dweight), N.ptr(dbias), N.ptr(y), 0 if y is None else y.size(1), N.ptr(ws),
+        ws.numel(), N.stream()), "mi355_hstu_ln_mul_dropout_bwd")
+    return dx, du, dweight, dbias, y
+
+
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        y, mean, rstd, block_d, num_warps = triton_weighted_layer_norm_fwd(x=x, weight=weight, bias=bias, eps=eps)
+        learnable = weight is not None
+        if learnable:
+            ctx.save_for_backward(x, weight, bias, mean, rstd)
+        else:
+            ctx.save_for_backward(x, mean, rstd)
+        ctx.launch = (block_d, num_warps)
+        ctx.eps, ctx.learnable = eps, learnable
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.learnable:
+            x, weight, bias, mean, rstd = ctx.saved_tensors
+        else:
+            (x, mean, rstd), weight, bias = ctx.saved_tensors, None, None
+        dx, dweight, dbias = triton_weighted_layer_norm_bwd(dy=dy, x=x, weight=weight, bias=bias, mean=mean, rstd=rstd,
+                                                            learnable=ctx.learnable, eps=ctx.eps, BLOCK_D=ctx.launch[0],
+                                                            num_warps=ctx.launch[1])
+        return dx, dweight, dbias, None
+
+
+class _LayerNormMulDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, u, weight, bias, eps, dropout_ratio, training, concat_ux, seed):
+        y, mean, rstd, block_d, num_warps, seed = triton_layer_norm_mul_dropout_fwd(
+            x=x, u=u, weight=weight, bias=bias, eps=eps, dropout_ratio=dropout_ratio, training=training, concat_ux=concat_ux,
+            seed=seed)
+        ctx.save_for_backward(x, u, weight, bias, mean, rstd)
+        ctx.launch = (block_d, num_warps)
+        ctx.eps, ctx.seed, ctx.training, ctx.concat_ux, ctx.dropout_ratio = eps, seed, training, concat_ux, dropout_ratio
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, u, weight, bias, mean, rstd = ctx.saved_tensors
+        dx, du, dweight, dbias, _ = triton_layer_norm_mul_dropout_bwd(
+            dy=dy, x=x, u=u, weight=weight, bias=bias, mean=mean, rstd=rstd, BLOCK_D=ctx.launch[0], num_warps=ctx.launch[1],
+            eps=ctx.eps, training=ctx.training, dropout_ratio=ctx.dropout_ratio, seed=ctx.seed, concat_ux=ctx.concat_ux,
+            compute_y=False)
+        return dx, du, dweight, dbias, None, None, None, None, None
+
+
+def triton_layer_norm(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float) -> torch.Tensor:
+    return _LayerNorm.apply(x, weight, bias, eps)
+
+
+def triton_norm_mul_dropout(x: torch.Tensor, u: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                            dropout_ratio: float, training: bool, concat_ux: bool = False, group_norm: bool = False,
+                            num_heads: int = 1, linear_dim: int = -1, seed: Optional[int] = None) -> torch.Tensor:
+    """y = dropout(ln(x, weight, bias) * u)"""
+    if group_norm:
+        raise NotImplementedError("group_norm is not implemented by the HIP norm ops")
+    return _LayerNormMulDropout.apply(x, u, weight, bias, eps, dropout_ratio, training, concat_ux, seed)
+
+
+layer_norm = triton_layer_norm
+norm_mul_dropout = triton_norm_mul_dropout
+weighted_layer_norm_fwd = triton_weighted_layer_norm_fwd
+weighted_layer_norm_bwd = triton_weighted_layer_norm_bwd
+layer_norm_mul_dropout_fwd = triton_layer_norm_mul_dropout_fwd
+layer_norm_mul_dropout_bwd = triton_layer_norm_mul_dropout_bwd

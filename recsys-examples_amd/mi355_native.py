@@ -19,6 +19,7 @@ c_i64 = ctypes.c_int64
 c_u64 = ctypes.c_uint64
 c_int = ctypes.c_int
 c_f = ctypes.c_float
+c_d = ctypes.c_double
 c_p = ctypes.c_void_p
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -201,6 +202,17 @@ _SIGS = {
                                                      c_p, c_i64, c_p, c_p, c_p],
     "mi355_hstu_index_rows_sum_workspace_bytes": [c_i64, c_i64, c_i64],
     "mi355_hstu_index_rows_sum": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p],
+    "mi355_hstu_layer_norm_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_int, c_f, c_p, c_i64, c_p, c_p, c_int, c_p],
+    "mi355_hstu_layer_norm_bwd_workspace_bytes": [c_i64, c_i64],
+    "mi355_hstu_layer_norm_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_int, c_p, c_p,  # dy, x, weight, stats
+                                  c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_ln_mul_dropout_fwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # x, u, rows, D, dtype
+                                      c_p, c_p, c_int, c_f, c_d, c_int, c_u64, c_int,  # weight, bias, eps, dropout
+                                      c_p, c_i64, c_p, c_p, c_p],
+    "mi355_hstu_ln_mul_dropout_bwd_workspace_bytes": [c_i64, c_i64],
+    "mi355_hstu_ln_mul_dropout_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # dy, x, u
+                                      c_p, c_p, c_int, c_p, c_p, c_d, c_int, c_u64, c_int,  # weight, stats, dropout
+                                      c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -230,6 +242,8 @@ _RESTYPES = {
     "mi355_hstu_fp8_blocks_bound": c_i64,
     "mi355_hstu_add_position_embeddings_bwd_workspace_bytes": c_i64,
     "mi355_hstu_index_rows_sum_workspace_bytes": c_i64,
+    "mi355_hstu_layer_norm_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_ln_mul_dropout_bwd_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
