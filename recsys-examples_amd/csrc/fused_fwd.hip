@@ -1492,6 +1492,32 @@ __device__ P3_EVICT_ATTR void part_evict(FusedArgs& a, int nd, int64_t rec_base,
       EST(9);
 }
 
+// A deferred record beyond the eviction budget of its partition block (kDefMax records per step) gets no eviction of its own.
+// Another record of the same key, inside the budget, may have placed the key in this step: then this record joins it -- every
+// occurrence of a key reads the same row and counts for its score and its update -- and otherwise the key has no slot this step
+// (like an insert that returns Busy).  Called behind the barrier that follows part_evict, whose stores are device-scope: so are
+// the loads.  zc: the record's slot code (-bucket - 2).  Returns the global slot, or S.
+template <typename IncT>
+__device__ __forceinline__ int over_budget_slot(const FusedArgs& a, int zc, uint64_t key, IncT inc) {
+  const int64_t bucket = -(int64_t)zc - 2;
+  const uint64_t* ks = a.t.keys(bucket);
+  const uint8_t* dg = a.t.dig(bucket);
+  const int C = (int)a.t.C;
+  const uint32_t d = digest_of((int64_t)(fmix64(key) & 0x7FFFFFFFFFFFFFFFull));
+  for (int p0 = 0; p0 < C; p0 += 16) {     // the key sits where the eviction found a victim: anywhere in the bucket
+    uint32_t m = eq_mask16(load_dig16(dg + p0, true), d);
+    while (m) {
+      const int s = p0 + __ffs(m) - 1;
+      m &= m - 1;
+      if (ald64(ks + s) == key) {
+        score_found(a, a.t.scores(bucket) + (int64_t)s * a.t.ns, inc);
+        return (int)(bucket * a.t.C + s);
+      }
+    }
+  }
+  return (int)a.S;
+}
+
 // every block of the probe kernel has retired when a partition block starts: the overflow word of this step is final
 __device__ __forceinline__ void publish_notice(const FusedArgs& a) {
   const unsigned long long f = __hip_atomic_load(&a.hdr[a.ovf_word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.ovf_val ? 1ull : 0ull;
@@ -1589,12 +1615,8 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
       dj[k] = atomicAdd(&s_nd, 1);
       if (dj[k] < kDefMax) {
         d_rec[dj[k]] = (short)idx;
-      } else {                           // beyond what one step evicts for: no slot this step (like an insert that returns Busy)
+      } else {                           // beyond what one step evicts for: resolved behind the eviction (over_budget_slot)
         dj[k] = -2;
-        bool cl;
-        en[k] = p2_insert<kP2Hash>(h_slot, (int)a.S, &cl);
-        mine[k] = cl;
-        bs[k] = atomicAdd(&h_cnt[en[k]], cn);
       }
     }
   }
@@ -1643,12 +1665,21 @@ fused_part3_kernel(FusedArgs a, EmitOut o, int* __restrict__ ptr, int* __restric
   }
 #pragma unroll
   for (int k = 0; k < kP3Items; ++k)
-    if (dj[k] == -2) {   // beyond the eviction budget: the record says "no slot"
+    if (dj[k] == -2) {   // beyond the eviction budget: the slot another record of the key took in this step, or "no slot"
       const int64_t r = (int64_t)p * kPartCap + threadIdx.x + k * kP3Threads;
-      a.rec[r].z = (uint32_t)a.S;
-      a.rec[r].w = (uint32_t)((int)rc[k].w | kRecLate);
+      const int cn = (int)rc[k].w;
+      using IncT = typename std::conditional<kW, int64_t, int>::type;
+      IncT inc;
+      if constexpr (kW) inc = a.rec_w[r]; else inc = cn;
+      const int gslot = over_budget_slot(a, (int)rc[k].z, ky[k], inc);
+      bool cl;
+      en[k] = p2_insert<kP2Hash>(h_slot, gslot, &cl);
+      mine[k] = cl;
+      bs[k] = atomicAdd(&h_cnt[en[k]], cn);
+      a.rec[r].z = (uint32_t)gslot;
+      a.rec[r].w = (uint32_t)(cn | kRecLate);
     }
-  if (nd > 0) __syncthreads();      // (block uniform; without deferred keys the hash has not changed since the barrier above)
+  if (s_nd > 0) __syncthreads();    // (block uniform; without deferred keys the hash has not changed since the barrier above)
   // ---- one scan over the hash ENTRIES: local unique id, occurrence prefix, hot-list positions (entry order = unique order)
   const bool hots = hot.n_tasks != nullptr;
   int es[kP3Ent], ec[kP3Ent];

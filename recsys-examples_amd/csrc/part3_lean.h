@@ -95,13 +95,8 @@ __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* 
         const int dj = atomicAdd(&s_nd, 1);
         if (dj < kDefMax) {
           d_rec[dj] = idx;                         // (entry and rank base come from the eviction below)
-        } else {                                   // beyond what one step evicts for: no slot this step (like an insert that returns Busy)
-          bool cl;
-          en = p2_insert<HASH>(h_slot, (int)a.S, &cl);
-          if (cl) h_pl[en] = (int)rc.x;
-          bs = atomicAdd(&h_cnt[en], cn);
-          a.rec[rec_base + idx].z = (uint32_t)a.S;
-          a.rec[rec_base + idx].w = (uint32_t)(cn | kRecLate);
+        } else {                                   // beyond what one step evicts for: resolved behind the eviction (entry -1 marks it)
+          en = -1;
         }
       }
       a.rec_out4[rec_base + idx] = make_int4(en, bs, 0, 0);
@@ -119,6 +114,26 @@ __device__ __forceinline__ void part3_lean(FusedArgs& a, const EmitOut& o, int* 
       const int ent = d_ent[e], bs = d_base[e];
       if (((s_late[ent >> 5] >> (ent & 31)) & 1u) && bs == 0) h_pl[ent] = (int)a.rec[rec_base + d_rec[e]].x;
       a.rec_out4[rec_base + d_rec[e]] = make_int4(ent, bs, 0, 0);
+    }
+    if (s_nd > kDefMax) {      // (block uniform) records beyond the budget: the slot another record of the key took, or none
+      for (int f = tid; f < total; f += T) {     // (the thread that marked the record in the merge pass)
+        const int idx = rec_index(f);
+        if (a.rec_out4[rec_base + idx].x != -1) continue;
+        const uint4 rc = a.rec[rec_base + idx];
+        int64_t kp = (int64_t)rc.x;
+        kp = kp < a.n ? kp : a.n - 1;
+        const int cn = (int)rc.w;
+        using IncT = typename std::conditional<kW, int64_t, int>::type;
+        IncT inc;
+        if constexpr (kW) inc = a.rec_w[rec_base + idx]; else inc = cn;
+        const int gslot = over_budget_slot(a, (int)rc.z, a.keys[kp], inc);
+        bool cl;
+        const int en = p2_insert<HASH>(h_slot, gslot, &cl);
+        if (cl) h_pl[en] = (int)rc.x;
+        a.rec_out4[rec_base + idx] = make_int4(en, atomicAdd(&h_cnt[en], cn), 0, 0);
+        a.rec[rec_base + idx].z = (uint32_t)gslot;
+        a.rec[rec_base + idx].w = (uint32_t)(cn | kRecLate);
+      }
     }
     __syncthreads();
   }
