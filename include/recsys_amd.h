@@ -1149,6 +1149,28 @@ int mi355_hstu_ln_mul_dropout_bwd(const void* dy, int64_t dy_stride, const void*
                                   void* du, int64_t du_stride0, int64_t du_stride1, void* dweight, void* dbias, void* y,
                                   int64_t y_stride, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- HSTU activations (csrc/act_ops.hip) ----
+ * The two element-wise steps of the fused HSTU layer (examples/hstu/ops/fused_hstu_op.py) that lie between the GEMMs.  Rows are
+ * [rows, N] in fp32 / bf16 / fp16 (`dtype`), last dimension contiguous, every pointer with its own row stride in ELEMENTS
+ * (>= N when rows > 1).  All arithmetic is fp32 and every stored value is rounded once.  No host sync, no allocation,
+ * capturable.  rows == 0 or N == 0 is a successful no-op (the backward still writes dbias = 0). */
+
+/* triton_silu.py (_silu_forward) and the SILU epilogue of triton_addmm.py:_addmm_optional_silu_fwd:
+ * s = z / (1 + expf(-z)).  s may be z (in place: same pointer and stride). */
+int mi355_hstu_silu_fwd(const void* z, int64_t z_stride, int64_t rows, int64_t N, int dtype, void* s, int64_t s_stride,
+                        hipStream_t stream);
+
+/* triton_silu.py (_silu_backward), and with dbias the pair aten.silu_backward + torch.sum(dz, 0) of triton_addmm_silu_bwd
+ * (triton_addmm.py:278-309) in one pass: sig = 1 / (1 + expf(-z)), dz = g sig (1 + z (1 - sig)); dz may be g (in place).
+ * dbias non-null: dbias[c] = sum over rows of the fp32 dz[., c] BEFORE its rounding, in an order fixed by (rows, N) alone (no
+ * atomics, bitwise reproducible, the same for every dtype and layout), rounded once to dbias_dtype (fp32 or `dtype`); this needs
+ * workspace (16-byte aligned, mi355_hstu_silu_bwd_workspace_bytes(rows, N), contents irrelevant).  dbias null: no sums, no
+ * workspace. */
+int64_t mi355_hstu_silu_bwd_workspace_bytes(int64_t rows, int64_t N);
+int mi355_hstu_silu_bwd(const void* g, int64_t g_stride, const void* z, int64_t z_stride, int64_t rows, int64_t N, int dtype,
+                        void* dz, int64_t dz_stride, void* dbias, int dbias_dtype, void* workspace, int64_t workspace_bytes,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

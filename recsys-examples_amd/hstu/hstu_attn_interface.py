@@ -90,6 +90,14 @@ def _fn(name: str, t: torch.Tensor):
 
 
 
+def check_operand_type(dtype: torch.dtype, head_dim: int) -> None:
+    """the operand types the kernels exist for: what a caller that builds q, k, v itself can ask before it builds them"""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError("HSTU only supports fp16 and bf16 data type")      # (hstu_api.cpp:359-366)
+    if head_dim not in (32, 64, 128, 256):
+        raise RuntimeError("head_dim must be one of 32, 64, 128, 256")
+
+
 def _check_inputs(q, k, v, cu_q, cu_k, num_contexts, num_targets, window_size, rab, kv_cache, seqused_q, seqused_k):
     if rab is not None:
         # hstu_api.cpp:417-430: (batch, heads or 1, max_seqlen_k, max_seqlen_k), contiguous last dimension
@@ -119,8 +127,7 @@ def _check_inputs(q, k, v, cu_q, cu_k, num_contexts, num_targets, window_size, r
         raise ValueError("AssertError: target is True and causal is not True, this is undefined behavior")
     local = not (wl == -1 and wr in (-1, 0))
     causal = wr == 0 and not local
-    if q.shape[-1] not in (32, 64, 128, 256):
-        raise RuntimeError("head_dim must be one of 32, 64, 128, 256")
+    check_operand_type(q.dtype, q.shape[-1])
     return causal
 
 

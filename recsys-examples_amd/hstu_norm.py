@@ -2,7 +2,8 @@
 order, defaults and return tuples of the reference (examples/hstu/ops/triton_ops/triton_layer_norm.py:313-481, :881-887 and
 triton_norm_mul_dropout.py:361-525, :1148-1182), over the kernels of csrc/norm_ops.hip.
 
-* Binding them is a one-line import change in fused_hstu_op.py, paged_hstu_infer_layer.py and native_hstu_layer.py
+* fused_hstu_op.py of this package is built on them; paged_hstu_infer_layer.py and native_hstu_layer.py import them from
+  here, the paged layer together with `from hstu_addmm import torch_addmm_silu_fwd, triton_addmm_silu_fwd`
   (INTEGRATION.md §4).  There is no Triton here and no eager fallback: CPU tensors raise.
 * `BLOCK_D` and `num_warps` are the reference's launch parameters: computed by its formulas and returned, ignored when passed
   back in (the kernels choose their layout from D).

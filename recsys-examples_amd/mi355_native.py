@@ -213,6 +213,9 @@ _SIGS = {
     "mi355_hstu_ln_mul_dropout_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # dy, x, u
                                       c_p, c_p, c_int, c_p, c_p, c_d, c_int, c_u64, c_int,  # weight, stats, dropout
                                       c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p],
+    "mi355_hstu_silu_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p],
+    "mi355_hstu_silu_bwd_workspace_bytes": [c_i64, c_i64],
+    "mi355_hstu_silu_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_int, c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -244,6 +247,7 @@ _RESTYPES = {
     "mi355_hstu_index_rows_sum_workspace_bytes": c_i64,
     "mi355_hstu_layer_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_ln_mul_dropout_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_silu_bwd_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
