@@ -1149,6 +1149,70 @@ int mi355_hstu_ln_mul_dropout_bwd(const void* dy, int64_t dy_stride, const void*
                                   void* du, int64_t du_stride0, int64_t du_stride1, void* dweight, void* dbias, void* y,
                                   int64_t y_stride, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- HSTU norm family (csrc/group_norm_ops.hip, csrc/norm_family_ops.hip) ----
+ * Group norm mul dropout, swish layer norm and RMS norm under the conventions of the layer norms above: fp32 arithmetic, every
+ * stored value rounded once; rows fp32 / bf16 / fp16, weights fp32 or of the row dtype; a row stride in ELEMENTS per row tensor,
+ * last dimension contiguous; row width 1 .. 8192; no host sync, no allocation, capturable; no atomics, every output bitwise
+ * reproducible.  rows == 0 is a successful no-op; a backward with rows == 0 still writes zero parameter gradients (so dweight /
+ * dbias are needed then, the workspace is not). */
+
+/* _group_norm_mul_dropout_fwd (triton_norm_mul_dropout.py:601-686, :842-911; pt_ops/pt_norm_mul_dropout.py:38-45).  x is
+ * [rows, H L] (D == H L), u [rows, H, L] with strides (u_stride0, u_stride1, 1) (a 2-D u: u_stride1 = L); weight and bias [H],
+ * both required; mean and rstd fp32 [rows H] at row H + h.  Per (row, head): mean = sum(x) / L, var = sum((x - mean)^2) / L in
+ * a second pass over the head, rstd = 1 / sqrtf(var + eps), xh = (x - mean) rstd, gn = fmaf(xh, w_h, b_h), t = gn u.
+ * y [rows, H L] = drop(t), or with concat_ux y [rows, 3 H L] = [drop0(u) | drop1(x) | drop2(t)]; the dropout is the stream
+ * defined above with col the column in the whole row, h L + c: with H == 1 the masks are those of
+ * mi355_hstu_ln_mul_dropout_fwd for the same seed. */
+int mi355_hstu_gn_mul_dropout_fwd(const void* x, int64_t x_stride, const void* u, int64_t u_stride0, int64_t u_stride1, int64_t H,
+                                  int64_t L, int64_t rows, int64_t D, int dtype, const void* weight, const void* bias,
+                                  int weight_dtype, float eps, double dropout_ratio, int training, uint64_t seed, int concat_ux,
+                                  void* y, int64_t y_stride, float* mean, float* rstd, hipStream_t stream);
+
+/* _group_norm_mul_dropout_bwd_dx_du + _group_norm_bwd_dwdb (triton_norm_mul_dropout.py:689-839, :914-1039).  The masks are made
+ * again from the seed.  dy is [rows, D], or [rows, 3 D] = [dy_u | dy_x | dy_t] with concat_ux.  dt = drop2'(dy_t);
+ * du = dt gn (+ drop0'(dy_u)), written with the strides of du (layout of u); per head g = w_h dt u, c1 = sum(xh g) / L,
+ * c2 = sum(g) / L, dx = (g - (xh c1 + c2)) rstd (+ drop1'(dy_x)); dweight[h] = sum over rows and the head's columns of dt u xh,
+ * dbias[h] likewise of dt u: fp32 sums in an order fixed by (rows, H, L) and the 16-byte alignment of the pointers and strides,
+ * rounded once to weight_dtype.  y non-null: the forward's output is written again, bit-equal to the forward's.  workspace:
+ * 16-byte aligned, mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(rows, H, L), contents irrelevant. */
+int64_t mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(int64_t rows, int64_t H, int64_t L);
+int mi355_hstu_gn_mul_dropout_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, const void* u,
+                                  int64_t u_stride0, int64_t u_stride1, int64_t H, int64_t L, int64_t rows, int64_t D, int dtype,
+                                  const void* weight, const void* bias, int weight_dtype, const float* mean, const float* rstd,
+                                  double dropout_ratio, int training, uint64_t seed, int concat_ux, void* dx, int64_t dx_stride,
+                                  void* du, int64_t du_stride0, int64_t du_stride1, void* dweight, void* dbias, void* y,
+                                  int64_t y_stride, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* SwishLayerNormFunction.forward (triton_layer_norm.py:763-816; the IS_SWISH branch of _weighted_layer_norm_fwd).  weight and
+ * bias [D], both required.  mean, rstd, xh and ln = fmaf(xh, w, b) as in mi355_hstu_layer_norm_fwd; s = 1 / (1 + expf(-ln)),
+ * evaluated as the sigmoid of mi355_hstu_silu_bwd; y = s x.  Writes mean and rstd. */
+int mi355_hstu_swish_layer_norm_fwd(const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype, const void* weight,
+                                    const void* bias, int weight_dtype, float eps, void* y, int64_t y_stride, float* mean,
+                                    float* rstd, hipStream_t stream);
+
+/* SwishLayerNormFunction.backward (triton_layer_norm.py:818-877; the IS_SWISH branch of _weighted_layer_norm_bwd_dx, :229-253).
+ * q = ((dy x) s) (1 - s), g = w q, c1 = sum(xh g) / D, c2 = sum(g) / D, dx = (g - (xh c1 + c2)) rstd + dy s;
+ * dweight = sum_rows q xh, dbias = sum_rows q in weight_dtype.  workspace: 16-byte aligned,
+ * mi355_hstu_swish_layer_norm_bwd_workspace_bytes(rows, D). */
+int64_t mi355_hstu_swish_layer_norm_bwd_workspace_bytes(int64_t rows, int64_t D);
+int mi355_hstu_swish_layer_norm_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, int64_t rows, int64_t D,
+                                    int dtype, const void* weight, const void* bias, int weight_dtype, const float* mean,
+                                    const float* rstd, void* dx, int64_t dx_stride, void* dweight, void* dbias, void* workspace,
+                                    int64_t workspace_bytes, hipStream_t stream);
+
+/* _weighted_rms_norm_fwd (triton_layer_norm.py:537-568, :660-704).  weight [D], required; no bias, no mean.
+ * rstd = 1 / sqrtf(sum(x^2) / D + eps), xh = x rstd, y = xh w.  Writes rstd. */
+int mi355_hstu_rms_norm_fwd(const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype, const void* weight,
+                            int weight_dtype, float eps, void* y, int64_t y_stride, float* rstd, hipStream_t stream);
+
+/* _weighted_rms_norm_bwd_dx + _rms_norm_bwd_dwdb (triton_layer_norm.py:571-657, :706-760).  xh = x rstd, g = w dy,
+ * c1 = sum(xh g) / D, dx = (g - xh c1) rstd; dweight = sum_rows dy xh in weight_dtype.  workspace: 16-byte aligned,
+ * mi355_hstu_rms_norm_bwd_workspace_bytes(rows, D). */
+int64_t mi355_hstu_rms_norm_bwd_workspace_bytes(int64_t rows, int64_t D);
+int mi355_hstu_rms_norm_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype,
+                            const void* weight, int weight_dtype, const float* rstd, void* dx, int64_t dx_stride, void* dweight,
+                            void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- HSTU activations (csrc/act_ops.hip) ----
  * The two element-wise steps of the fused HSTU layer (examples/hstu/ops/fused_hstu_op.py) that lie between the GEMMs.  Rows are
  * [rows, N] in fp32 / bf16 / fp16 (`dtype`), last dimension contiguous, every pointer with its own row stride in ELEMENTS

@@ -213,6 +213,20 @@ _SIGS = {
     "mi355_hstu_ln_mul_dropout_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # dy, x, u
                                       c_p, c_p, c_int, c_p, c_p, c_d, c_int, c_u64, c_int,  # weight, stats, dropout
                                       c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p],
+    "mi355_hstu_gn_mul_dropout_fwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # x, u, H, L, rows, D, dtype
+                                      c_p, c_p, c_int, c_f, c_d, c_int, c_u64, c_int,  # weight, bias, eps, dropout
+                                      c_p, c_i64, c_p, c_p, c_p],
+    "mi355_hstu_gn_mul_dropout_bwd_workspace_bytes": [c_i64, c_i64, c_i64],
+    "mi355_hstu_gn_mul_dropout_bwd": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,  # dy, x, u
+                                      c_p, c_p, c_int, c_p, c_p, c_d, c_int, c_u64, c_int,  # weight, stats, dropout
+                                      c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p],
+    "mi355_hstu_swish_layer_norm_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_int, c_f, c_p, c_i64, c_p, c_p, c_p],
+    "mi355_hstu_swish_layer_norm_bwd_workspace_bytes": [c_i64, c_i64],
+    "mi355_hstu_swish_layer_norm_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_p,  # dy, x, w, b, stats
+                                        c_p, c_i64, c_p, c_p, c_p, c_i64, c_p],
+    "mi355_hstu_rms_norm_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_int, c_f, c_p, c_i64, c_p, c_p],
+    "mi355_hstu_rms_norm_bwd_workspace_bytes": [c_i64, c_i64],
+    "mi355_hstu_rms_norm_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_int, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p],
     "mi355_hstu_silu_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p],
     "mi355_hstu_silu_bwd_workspace_bytes": [c_i64, c_i64],
     "mi355_hstu_silu_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_int, c_p, c_i64, c_p],
@@ -247,6 +261,9 @@ _RESTYPES = {
     "mi355_hstu_index_rows_sum_workspace_bytes": c_i64,
     "mi355_hstu_layer_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_ln_mul_dropout_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_gn_mul_dropout_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_swish_layer_norm_bwd_workspace_bytes": c_i64,
+    "mi355_hstu_rms_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_silu_bwd_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
