@@ -1235,6 +1235,50 @@ int mi355_hstu_silu_bwd(const void* g, int64_t g_stride, const void* z, int64_t 
                         void* dz, int64_t dz_stride, void* dbias, int dbias_dtype, void* workspace, int64_t workspace_bytes,
                         hipStream_t stream);
 
+/* ---- jagged x dense products (csrc/jagged_bmm.hip) ----
+ * The jagged-dense ops of examples/commons/ops/triton_ops/triton_jagged.py.  A jagged tensor is [L, width] rows in fp32 / bf16 /
+ * fp16 (`dtype`), last dimension contiguous, with a row stride in ELEMENTS (>= the width when L > 1); `offsets` is int64
+ * [batch + 1] on the device, sample b owning the rows offsets[b] .. offsets[b + 1] - 1.  Offsets are clamped to [0, L]; rows at
+ * or past offsets[batch] belong to no sample and are never read.  The grids are sized from L and batch alone: no host read of an
+ * offset, no max_seq_len, no allocation, capturable.  All arithmetic is fp32, every stored value is rounded once; no atomics,
+ * every output bitwise reproducible.  L == 0 is a successful no-op for the per-row outputs; the per-sample outputs are still
+ * written (zeros). */
+
+/* jagged_dense_bmm_broadcast_add_kernel (triton_jagged.py:77-153; its callers :258-363 and :540-648).
+ * out[r, :N] = jagged[r, :K] . dense_b[K, N] (+ bias[b, :N]) for the rows r of sample b; dense_b[k, n] is read at
+ * dense + b stride_db + k stride_dk + n stride_dn (elements), so the backward's d_jagged = d_out . dense_b^T is this entry point
+ * with stride_dk and stride_dn swapped and bias null.  bias may be null; bias_stride is its row stride.  Rows of `out` at or
+ * past offsets[batch] are written as zeros.  bf16 / fp16: v_mfma_f32_32x32x16; fp32: v_mfma_f32_32x32x2_f32 (an fmaf chain in k
+ * order).  The bias is added to the fp32 sum before the rounding. */
+int mi355_jagged_dense_bmm(const void* jagged, int64_t jagged_stride, const int64_t* offsets, int64_t batch, int64_t L, int64_t K,
+                           int64_t N, const void* dense, int64_t stride_db, int64_t stride_dk, int64_t stride_dn,
+                           const void* bias, int64_t bias_stride, void* out, int64_t out_stride, int dtype, hipStream_t stream);
+
+/* _jagged_jagged_bmm_reduce_sum (triton_jagged.py:161-255).  out[b, :M, :N] = a_rows[rows of b, :M]^T . b_rows[rows of b, :N], at
+ * out + b out_stride_b + m out_stride_m + n; col_sum non-null: col_sum[b, :N] = sum over the rows of b of b_rows (row stride
+ * col_sum_stride), taken by the same MFMAs against a tile of ones, in the order of out.  These are d_dense and d_bias of
+ * mi355_jagged_dense_bmm.  An empty sample writes zeros.  A sample is summed in row order in chunks of C rows counted from its
+ * first row (C = 64 rows per 64 x 64 tile of out, within 256 .. 4096: a function of M and N); the chunk sums of a sample longer
+ * than C go through `workspace` and are added in chunk order, so the order of all additions is a function of (length, M, N)
+ * alone.  workspace: 16-byte aligned, mi355_jagged_jagged_bmm_workspace_bytes(batch, L, M, N), contents irrelevant. */
+int64_t mi355_jagged_jagged_bmm_workspace_bytes(int64_t batch, int64_t L, int64_t M, int64_t N);
+int mi355_jagged_jagged_bmm(const void* a_rows, int64_t a_stride, const void* b_rows, int64_t b_stride, const int64_t* offsets,
+                            int64_t batch, int64_t L, int64_t M, int64_t N, void* out, int64_t out_stride_b, int64_t out_stride_m,
+                            void* col_sum, int64_t col_sum_stride, int dtype, void* workspace, int64_t workspace_bytes,
+                            hipStream_t stream);
+
+/* jagged_dense_broadcast_add_kernel (triton_jagged.py:387-437).  out[r, :D] = jagged[r, :D] + dense[b, :D] for the rows r of
+ * sample b: one fp32 add, one rounding.  Rows at or past offsets[batch] are written as zeros.  16-byte accesses where D, every
+ * base pointer and every stride allow, else element by element (same values). */
+int mi355_jagged_broadcast_add(const void* jagged, int64_t jagged_stride, const int64_t* offsets, int64_t batch, int64_t L,
+                               int64_t D, const void* dense, int64_t dense_stride, void* out, int64_t out_stride, int dtype,
+                               hipStream_t stream);
+
+/* jagged_reduce_sum (triton_jagged.py:440-477).  out[b, :D] = sum over the rows of sample b (zeros for an empty one): fp32,
+ * 16 interleaved runs in row order folded in run order (a function of the length alone), rounded once. */
+int mi355_jagged_row_sum(const void* jagged, int64_t jagged_stride, const int64_t* offsets, int64_t batch, int64_t L, int64_t D,
+                         void* out, int64_t out_stride, int dtype, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,13 @@ _SIGS = {
     "mi355_hstu_silu_fwd": [c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p],
     "mi355_hstu_silu_bwd_workspace_bytes": [c_i64, c_i64],
     "mi355_hstu_silu_bwd": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_int, c_p, c_i64, c_p],
+    "mi355_jagged_dense_bmm": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64,
+                               c_int, c_p],
+    "mi355_jagged_jagged_bmm_workspace_bytes": [c_i64, c_i64, c_i64, c_i64],
+    "mi355_jagged_jagged_bmm": [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_int,
+                                c_p, c_i64, c_p],
+    "mi355_jagged_broadcast_add": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_p],
+    "mi355_jagged_row_sum": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_int, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -265,6 +272,7 @@ _RESTYPES = {
     "mi355_hstu_swish_layer_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_rms_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_silu_bwd_workspace_bytes": c_i64,
+    "mi355_jagged_jagged_bmm_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
