@@ -788,6 +788,34 @@ int mi355_append_kvcache(void* kv_cache, const int32_t* kv_indices, const int32_
                          const int32_t* batch_indices, const int32_t* positions, const int32_t* seqlen_offsets,
                          const int32_t* nnz_dev, int64_t max_nnz, int64_t nnz_upper, hipStream_t stream);
 
+/* KV cache GPU tier (csrc/kvcache_ops.hip; 16-bit type-agnostic like mi355_append_kvcache).
+ *
+ * mi355_kvcache_move_pages: the page mover of the cache [L, P, 2, page_size, H, D], both directions, every layer of a range in
+ * one launch (gather_kvcache and GatherPagedKVCacheAllLayers, examples/commons/ops/cuda_ops/csrc/paged_kvcache_ops_kernel.cu:
+ * 237-429 and paged_kvcache_ops_cuda.cpp:229-321; the gather / scatter kernels of corelib/recsys_kvcache_manager/src/
+ * gather_scatter_kernels.cu).  direction 0 (gather, offload): staging slot j of layer l becomes a bit-exact copy of page
+ * page_ids[j] of layer l; direction 1 (scatter, onboard): the inverse.  A page is page_elems = 2 * page_size * H * D contiguous
+ * elements in either kv_layout, so the mover is layout-agnostic.  cache points at the first layer of the range; the strides
+ * between pages and between layers are given in elements for cache and staging separately and must be multiples of 8, both
+ * pointers 16-byte aligned.  All offsets are 64 bits wide.  page_ids is int32 on the device, num_pages comes from the host: no
+ * sync, no allocation, graph-capturable; num_pages == 0 returns without a launch.  A slot whose id is outside
+ * [0, num_cache_pages) is skipped -- nothing is read or written, on a gather its staging slot keeps what it held.  Duplicate
+ * ids in a scatter: which copy wins is undefined; in a gather they are fine.  grid_cap (256-thread blocks) and nontemporal (1:
+ * nontemporal loads and stores, 0: plain) are measurement knobs: 0 and -1 select the measured defaults
+ * (profiles/kvcache_pages_bench.txt).
+ *
+ * mi355_kvcache_batch_positions: the append metadata of a batch (GetPagedBatchIndicesPositions, paged_kvcache_ops_kernel.cu:
+ * 451-492, called from gpu_kvcache_manager_impl.cpp:379-386).  Token i of sequence b (new_history_offsets[b] <= i <
+ * new_history_offsets[b + 1]) gets batch_indices[i] = b and positions[i] = total_history_lengths[b] - (new_history_offsets[b + 1]
+ * - new_history_offsets[b]) + (i - new_history_offsets[b]).  One thread per token; nnz = new_history_offsets[batch] comes from
+ * the host. */
+int mi355_kvcache_move_pages(int direction, void* cache, void* staging, const int32_t* page_ids, int64_t num_pages,
+                             int64_t num_cache_pages, int64_t num_layers, int64_t page_elems, int64_t cache_page_stride,
+                             int64_t cache_layer_stride, int64_t staging_page_stride, int64_t staging_layer_stride,
+                             int64_t grid_cap, int nontemporal, hipStream_t stream);
+int mi355_kvcache_batch_positions(const int32_t* new_history_offsets, const int32_t* total_history_lengths, int64_t batch,
+                                  int64_t nnz, int32_t* batch_indices, int32_t* positions, hipStream_t stream);
+
 /* hstu_varlen_bwd (hstu_api.cpp:525-719; hstu_varlen_bwd_80, fused_hstu_op.py:682-706): dq, dk, dv
  * contiguous bf16 [total, H, d].  Deterministic (two passes, no atomics): `deterministic` of the
  * reference is always on. */

@@ -237,6 +237,8 @@ _SIGS = {
                                 c_p, c_i64, c_p],
     "mi355_jagged_broadcast_add": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_p],
     "mi355_jagged_row_sum": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_int, c_p],
+    "mi355_kvcache_move_pages": [c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_p],
+    "mi355_kvcache_batch_positions": [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
