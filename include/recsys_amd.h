@@ -1307,6 +1307,66 @@ int mi355_jagged_broadcast_add(const void* jagged, int64_t jagged_stride, const 
 int mi355_jagged_row_sum(const void* jagged, int64_t jagged_stride, const int64_t* offsets, int64_t batch, int64_t L, int64_t D,
                          void* out, int64_t out_stride, int dtype, hipStream_t stream);
 
+/* ---- the FBGEMM sparse / jagged ops that examples/hstu calls as torch.ops.fbgemm.* (csrc/fbgemm_jagged.hip) ----
+ * Reference paths below are relative to the reference's examples/.  Pure data movement: bit-exact, no read-modify-write
+ * atomics, no host read, no allocation, capturable, 64-bit addressing.  `*_itype` is the type of an offsets / lengths / indices
+ * vector: 0 = int32, 1 = int64 (read as they are, never converted).  Values are moved as bytes: `elem_bytes` is the element
+ * size, not a dtype code. */
+
+/* asynchronous_complete_cumsum / _inclusive_cumsum / _exclusive_cumsum (hstu/modules/jagged_data.py:125,133,142,
+ * hstu/modules/hstu_processor.py:169,185, hstu/ops/jagged_tensor_op.py:60, commons/ops/length_to_offsets.py:20,25,30).
+ * in: [rows, n] of int32 / int64 (`itype`).  mode 0 (complete): out is [rows, n + 1], out[r, 0] = 0 and out[r, i + 1] =
+ * in[r, 0] + .. + in[r, i]; mode 1 (inclusive) and 2 (exclusive): out is [n], rows must be 1.  Sums wrap in the dtype as
+ * torch.cumsum's do.  One pass over the data for any n: one block per row up to 8192 elements, above that a decoupled
+ * look-back over 4096-element tiles, whose status words live in `workspace` (16-byte aligned,
+ * mi355_cumsum_workspace_bytes(rows, n) bytes, 0 for the one-block case; contents irrelevant: the call clears them with a
+ * small launch of its own in front of the scan).  A look-back launch holds one tile per block and no more tiles than the
+ * device keeps resident (2 blocks per CU of the current device's CU count, about 2 M elements on 256 CUs); a longer input
+ * takes further launches on the stream, each continuing from the output of the one before.  A block waits only for
+ * lower-numbered blocks of its own launch, and every wait is bounded (seconds): if one ever runs out, the tiles concerned stay
+ * UNWRITTEN, the call has long returned MI355_OK, and the only trace is the first 8 bytes of `workspace`, non-zero once the
+ * stream has finished (zero after every healthy call).
+ * rows == 0 or n == 0 launches nothing (the caller provides the [rows, 1] zeros of the complete sum). */
+int64_t mi355_cumsum_workspace_bytes(int64_t rows, int64_t n);
+int mi355_cumsum(const void* in, void* out, int64_t rows, int64_t n, int itype, int mode, void* workspace,
+                 int64_t workspace_bytes, hipStream_t stream);
+
+/* jagged_to_padded_dense / jagged_2d_to_dense (hstu/ops/jagged_tensor_op.py:66,105,111, hstu/ops/pt_ops/
+ * pt_hstu_attention.py:117-137,247,257), and the backward of dense_to_jagged.  values: [T, D] with row stride D; offsets:
+ * [B + 1]; out: [B, max_len, D] contiguous.  out[b, l, :] = values[offsets[b] + l, :] for l < min(len_b, max_len), else the
+ * padding element, whose raw bits are `padding_bits` (the low elem_bytes bytes; so int64 -1 is as good as bf16 0.5); a sample
+ * longer than max_len is truncated.  Every element of out is written exactly once, the padding included (no memset).
+ * elem_bytes 2, 4 or 8; any D >= 1: 16-byte accesses where D elem_bytes and both base pointers allow, narrower otherwise.
+ * A row index outside [0, T) (inconsistent offsets) reads nothing and gives padding. */
+int mi355_jagged_to_padded(const void* values, int64_t T, const void* offsets, int offsets_itype, int64_t B, int64_t max_len,
+                           int64_t D, int elem_bytes, uint64_t padding_bits, void* out, hipStream_t stream);
+
+/* dense_to_jagged (hstu/ops/jagged_tensor_op.py:74,78 -- on the slices dense[:, :-n] and dense[:, n:] --,
+ * hstu/ops/pt_ops/pt_hstu_attention.py:192), and the backward of the two to-dense ops.  dense: [B, N, D], element (b, l, d) at
+ * dense + b stride_b + l stride_n + d (strides in ELEMENTS, inner dimension contiguous); out: [total, D] contiguous.
+ * out[offsets[b] + l, :] = dense[b, l, :] for l < N, zeros for N <= l < len_b (FBGEMM allocates zeros).  Rows of out at or
+ * past offsets[B] belong to no sample: they are written as zeros too (FBGEMM's zero allocation again, and what the backward of
+ * jagged_to_padded_dense needs for value rows outside every sample), so every element of out is written exactly once. */
+int mi355_padded_to_jagged(const void* dense, int64_t stride_b, int64_t stride_n, int64_t B, int64_t N, const void* offsets,
+                           int offsets_itype, int64_t D, int elem_bytes, void* out, int64_t total, hipStream_t stream);
+
+/* keyed_jagged_index_select_dim1 (commons/sequence_batch/batch.py:144, commons/distributed/batch_all2all.py:165,254,
+ * commons/ops/collective_ops.py:602: the batch shuffler).  A KeyedJaggedTensor of F features x B samples: lengths [F B],
+ * offsets [F B + 1], values [num_values]; indices [S] selects samples: output bag (f, j) is input bag (f, indices[j]).
+ * mi355_kjt_select_lengths writes out_lengths [F S] (the type of lengths); its complete cumsum (mi355_cumsum, mode 0) is
+ * out_offsets [F S + 1]; mi355_kjt_select_values then moves the bag contents into out_values [total] -- values of 1, 2, 4 or 8
+ * bytes per element, and, when weights is non-null, weights (2, 4 or 8 bytes) into out_weights in the same launch.  One lane
+ * per output element, so a bag of thousands of ids is spread like any other elements.
+ * An index outside [0, B) yields an EMPTY bag (length 0, nothing moved): it is not a fault, and not undefined as it is in
+ * FBGEMM.  Elements of out_values at or past out_offsets[F S], and elements whose source would lie outside its bag or outside
+ * [0, num_values), are written as zeros; nothing outside the buffers is read or written whatever the vectors hold. */
+int mi355_kjt_select_lengths(const void* lengths, int lengths_itype, const void* indices, int indices_itype, int64_t F,
+                             int64_t B, int64_t S, void* out_lengths, hipStream_t stream);
+int mi355_kjt_select_values(const void* values, int64_t num_values, int elem_bytes, const void* weights, int weight_bytes,
+                            const void* offsets, int offsets_itype, const void* indices, int indices_itype, int64_t F,
+                            int64_t B, int64_t S, const void* out_offsets, int out_offsets_itype, void* out_values,
+                            void* out_weights, int64_t total, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

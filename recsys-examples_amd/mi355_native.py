@@ -239,6 +239,13 @@ _SIGS = {
     "mi355_jagged_row_sum": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_int, c_p],
     "mi355_kvcache_move_pages": [c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_p],
     "mi355_kvcache_batch_positions": [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p],
+    "mi355_cumsum_workspace_bytes": [c_i64, c_i64],
+    "mi355_cumsum": [c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_i64, c_p],
+    "mi355_jagged_to_padded": [c_p, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_int, c_u64, c_p, c_p],
+    "mi355_padded_to_jagged": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_int, c_i64, c_int, c_p, c_i64, c_p],
+    "mi355_kjt_select_lengths": [c_p, c_int, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_p],
+    "mi355_kjt_select_values": [c_p, c_i64, c_int, c_p, c_int, c_p, c_int, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_int, c_p,
+                                c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -275,6 +282,7 @@ _RESTYPES = {
     "mi355_hstu_rms_norm_bwd_workspace_bytes": c_i64,
     "mi355_hstu_silu_bwd_workspace_bytes": c_i64,
     "mi355_jagged_jagged_bmm_workspace_bytes": c_i64,
+    "mi355_cumsum_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
