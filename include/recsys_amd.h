@@ -1367,6 +1367,37 @@ int mi355_kjt_select_values(const void* values, int64_t num_values, int elem_byt
                             int64_t B, int64_t S, const void* out_offsets, int out_offsets_itype, void* out_values,
                             void* out_weights, int64_t total, hipStream_t stream);
 
+/* ---- beam-search decode attention of the semantic-ID generative-retrieval family (csrc/beam_decode.hip) ----
+ * beam_decode_attn / BeamDecodeAttn (corelib/gr_decode_atten/interface.py:635-942; semantics: tests/reference.py there,
+ * beam_attention_ref).  For batch b, beam w, query head h (kv head h / G, G = Hq / Hkv) the key set is the Sk_b context rows
+ * of sample b followed by the beam rows k_beam[b, topk[b, 0, (h / G) G, n, w], h / G] for n < decode_nums; scores are
+ * softmax_scale q.k; out = softmax(scores) V in `dtype` (1 = bf16, 2 = fp16, the type of every q / k / v), lse =
+ * logsumexp(scores) in fp32.  A row with no key gives out = 0, lse = -inf.  A beam index outside [0, decode_nums W) is never
+ * dereferenced: that key is absent.  A repeated index counts twice.
+ *   q: element (b, w, h, d) at q + b q_stride_b + w q_stride_w + h q_stride_h + d; out [B, W, Hq, D] and lse [B, W, Hq] contiguous.
+ *   context, dense (cu_seqlens_k null): [B, Sk, Hkv, D] at the given batch / row / head strides; Sk_b = Sk, or
+ *     min(seqused_k[b], Sk) when seqused_k is non-null.  Jagged (cu_seqlens_k [B + 1] non-null): [total_k, Hkv, D], rows
+ *     cu_seqlens_k[b] .. cu_seqlens_k[b + 1] (clamped to [0, total_k]); the batch strides and Sk are ignored.  seqused_k and
+ *     cu_seqlens_k are mutually exclusive.
+ *   beam: k_beam / v_beam [B, decode_nums W, Hkv, D] at the given strides; topk_indices (topk_itype 0 = int32, 1 = int64):
+ *     element (b, 0, h, n, w) at b tk_stride_b + h tk_stride_h + n tk_stride_n + w tk_stride_w.
+ * All strides are in elements; every q / k / v base pointer is 16-byte aligned and every q / k / v stride a multiple of 8.
+ * D is 64 or 128.  num_splits >= 1 splits each sample's own key tiles (64 keys) into that many ranges, with any context
+ * form; the fp32 partials live in `workspace` (16-byte aligned, mi355_beam_decode_workspace_bytes(B, W, Hq, D, num_splits)
+ * bytes, contents irrelevant).  Two launches, no atomics: bitwise reproducible for a given num_splits.  No host read,
+ * no allocation, capturable. */
+int64_t mi355_beam_decode_workspace_bytes(int64_t B, int64_t W, int64_t Hq, int64_t D, int64_t num_splits);
+int mi355_beam_decode_attn(const void* q, int64_t q_stride_b, int64_t q_stride_w, int64_t q_stride_h, const void* k_context,
+                           const void* v_context, int64_t kc_stride_b, int64_t kc_stride_s, int64_t kc_stride_h,
+                           int64_t vc_stride_b, int64_t vc_stride_s, int64_t vc_stride_h, int64_t Sk, int64_t total_k,
+                           const int32_t* seqused_k, const int32_t* cu_seqlens_k, const void* k_beam, const void* v_beam,
+                           int64_t kb_stride_b, int64_t kb_stride_s, int64_t kb_stride_h, int64_t vb_stride_b,
+                           int64_t vb_stride_s, int64_t vb_stride_h, const void* topk_indices, int topk_itype,
+                           int64_t tk_stride_b, int64_t tk_stride_h, int64_t tk_stride_n, int64_t tk_stride_w, int64_t B,
+                           int64_t W, int64_t Hq, int64_t Hkv, int64_t D, int64_t decode_nums, float softmax_scale,
+                           int64_t num_splits, void* out, float* lse, int dtype, void* workspace, int64_t workspace_bytes,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

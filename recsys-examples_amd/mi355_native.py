@@ -246,6 +246,12 @@ _SIGS = {
     "mi355_kjt_select_lengths": [c_p, c_int, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_p],
     "mi355_kjt_select_values": [c_p, c_i64, c_int, c_p, c_int, c_p, c_int, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_int, c_p,
                                 c_p, c_i64, c_p],
+    "mi355_beam_decode_workspace_bytes": [c_i64, c_i64, c_i64, c_i64, c_i64],
+    "mi355_beam_decode_attn": [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # q, context
+                               c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # lengths, beam
+                               c_p, c_int, c_i64, c_i64, c_i64, c_i64,  # top-k indices
+                               c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_i64,  # B, W, Hq, Hkv, D, decode_nums, scale, splits
+                               c_p, c_p, c_int, c_p, c_i64, c_p],
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
@@ -283,6 +289,7 @@ _RESTYPES = {
     "mi355_hstu_silu_bwd_workspace_bytes": c_i64,
     "mi355_jagged_jagged_bmm_workspace_bytes": c_i64,
     "mi355_cumsum_workspace_bytes": c_i64,
+    "mi355_beam_decode_workspace_bytes": c_i64,
     "mi355_last_error": ctypes.c_char_p,
 }
 _OPTIONAL_SIGS = {}  # filled by optional modules (e.g. hstu) before first load
