@@ -1398,6 +1398,38 @@ int mi355_beam_decode_attn(const void* q, int64_t q_stride_b, int64_t q_stride_w
                            int64_t num_splits, void* out, float* lse, int dtype, void* workspace, int64_t workspace_bytes,
                            hipStream_t stream);
 
+/* ---- softmax prefill attention of the semantic-ID generative-retrieval family, forward (csrc/prefill_attn.hip) ----
+ * Replaces the flash-attention calls of examples/sid_gr/model/jagged_flash_attn_block.py and of sid-gr-inference's
+ * gr_kernels/prefill/flash_attn_backend.py: flash_attn.flash_attn_interface.flash_attn_varlen_func(q, k, v, cu_seqlens_q,
+ * cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, causal), flash_attn.flash_attn_func(q, k, v, softmax_scale, causal)
+ * and flash_attn.cute.interface.flash_attn_func(..., arbitrary=True, aux_tensors=[arbitrary_func]).
+ * For sequence b and query head h (kv head h / G, G = Hq / Hkv) with Lq queries and Lk keys, query i sees key j iff
+ *   mask 0 (none):    always;
+ *   mask 1 (causal):  j <= i + Lk - Lq (bottom-right aligned, flash-attn >= 2.1; a row with i + Lk - Lq < 0 sees nothing);
+ *   mask 2 (func):    j < F[0][i], or F[2p-1][i] <= j < F[2p][i] for some p >= 1 (interval ends clamped to [0, Lk], an interval
+ *                     with start >= end is empty), F = func[b, h or 0]: element (b, h, f, i) at func + b func_stride_b +
+ *                     h func_stride_h + f func_stride_f + i func_stride_s, int32, n_func odd, func_heads 1 or Hq; columns at or
+ *                     past Sq are never read.  Dense form only; func must be null for masks 0 and 1.
+ * scores = softmax_scale q.k; out = softmax(scores) V in `dtype` (1 = bf16, 2 = fp16, the type of q, k and v); lse =
+ * logsumexp(scores), natural log, fp32.  A row with no visible key gives out = 0 and lse = -inf exactly.
+ *   dense (cu_seqlens_q = cu_seqlens_k = null): q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] at the given batch / row / head strides;
+ *     out [B, Sq, Hq, D] and lse [B, Hq, Sq] contiguous.  total_q / total_k are ignored.
+ *   jagged (both non-null, int32 [B + 1]): q [total_q, Hq, D], k / v [total_k, Hkv, D] at the given row / head strides (the
+ *     batch strides and Sk are ignored); sequence b is rows cu[b] .. cu[b + 1], the bounds clamped into [0, total] and made
+ *     monotone, so that no row outside the tensors is read.  Sq is max_seqlen_q: query rows of a sequence at or past it are
+ *     not computed.  out [total_q, Hq, D] and lse [Hq, total_q] contiguous.
+ * All strides are in elements; every q / k / v / out base pointer is 16-byte aligned and every q / k / v stride a multiple of
+ * 8 (so views of one packed [B, S, 3, H, D] buffer are taken as they are).  D is 64 or 128.  skip_tiles: 1 (the default of
+ * the Python surface) visits only the key tiles (64 keys) that the rows of a workgroup (128 query rows) can see; 0 visits and
+ * tests all of them, with bitwise the same result.  One launch, no workspace, no atomics, no host read: capturable and bitwise reproducible. */
+int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, const void* k,
+                       int64_t k_stride_b, int64_t k_stride_s, int64_t k_stride_h, const void* v, int64_t v_stride_b,
+                       int64_t v_stride_s, int64_t v_stride_h, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                       int64_t B, int64_t Sq, int64_t Sk, int64_t total_q, int64_t total_k, int64_t Hq, int64_t Hkv, int64_t D,
+                       int mask, const int32_t* func, int64_t n_func, int64_t func_heads, int64_t func_stride_b,
+                       int64_t func_stride_h, int64_t func_stride_f, int64_t func_stride_s, float softmax_scale,
+                       int skip_tiles, void* out, float* lse, int dtype, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

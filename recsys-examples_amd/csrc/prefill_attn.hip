@@ -1,0 +1,421 @@
+// Softmax prefill attention (forward) of the semantic-ID generative-retrieval family: the kernel that builds the context the
+// beam-search decode kernels (beam_decode.hip) attend over.
+//
+// Replaces (reference): the three flash-attention calls of examples/sid_gr/model/jagged_flash_attn_block.py and
+// examples/sid-gr-inference/.../gr_kernels/prefill/flash_attn_backend.py -- flash_attn_varlen_func(causal=True) on a
+// flattened jagged batch, flash_attn_func(causal=True) on a padded batch, and flash_attn.cute's flash_attn_func(arbitrary=True,
+// aux_tensors=[arbitrary_func]) for the beam-isolation / target-aware masks.  flash_attn is CUDA / CuTe DSL; this is written
+// for gfx950 from the semantics (bottom-right aligned causal as in flash-attn >= 2.1; the interval encoding of arbitrary_func,
+// examples/sid_gr/model/attention_mask.py:210-275, which is the `func` of hstu_attn.hip).
+//
+// One launch, no workspace, no atomics: bitwise reproducible.  prefill_attn_kernel has the structure of beam_ctx_kernel:
+// v_mfma_f32_32x32x16_{bf16,f16}; one workgroup (4 waves) owns one (sequence, query head, tile of 128 query rows), a wave 32
+// rows, its Q fragments in registers; K / V come from kv head h / G.  Per tile of 64 keys K goes to LDS as [key][D + 8] and V
+// transposed as [d][64 + 4]; S^T = K Q^T puts the key index in the accumulator registers and the query row on the lane, so a
+// row's max and sum are per-lane reductions plus one exchange between the lane halves; P, rounded once to the operand type
+// (the row sum takes the fp32 P), is the B operand of O^T += V^T P^T with no trip through LDS.  Running max and sum are fp32 in
+// log2 units.  The global loads of the next tile are issued before the MFMAs of this one and written to LDS after them.
+//
+// Masks.  Every query row has a prefix bound `pre` (keys j < pre are seen) and, for the arbitrary kind, bands [lo, up):
+//   none     pre = Lk
+//   causal   pre = clamp(i + 1 + Lk - Lq, 0, Lk)                              (bottom-right aligned)
+//   func     pre = clamp(F[0][i], 0, Lk), bands clamp(F[2p-1][i]) .. clamp(F[2p][i]), an interval with start >= end is empty
+// A wave reduces the extents of its 32 rows (largest and smallest prefix, hull of the bands); the four waves' extents are
+// exchanged through LDS once.  A key tile is loaded only if some wave's prefix or hull reaches it, a wave computes only the
+// tiles its own rows reach, and the per-element test runs only on tiles that are not inside the smallest prefix of the wave.
+// A tile that is skipped would have had P = 0 for every row and the running max unchanged, so skipping changes no bit of the
+// result (skip_tiles = 0 turns the skipping off: every tile is loaded, computed and tested).
+//
+// A row with no visible key -- in a tile (m stays -inf: the exponent is taken against 0, so P = exp2(-inf) = 0 and no
+// inf - inf arises) or at all (l = 0: out = 0, lse = -inf).
+#include "common.h"
+#include "../../include/recsys_amd.h"
+
+#include <math.h>
+
+namespace mi355 {
+
+typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t pf_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t pf_u32x2 __attribute__((ext_vector_type(2)));
+typedef float pf_f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kPfKeys = 64;     // keys per tile
+constexpr int kPfRows = 128;    // query rows per workgroup (4 waves x 32)
+constexpr float kPfLog2e = 1.4426950408889634f;
+constexpr float kPfLn2 = 0.6931471805599453f;
+constexpr int kPfNone = 0, kPfCausal = 1, kPfFunc = 2;
+constexpr int kPfIntMax = 0x7fffffff;
+
+template <int DT> struct PfMma;
+template <> struct PfMma<kBF16> {
+  typedef __bf16 V8 __attribute__((ext_vector_type(8)));
+  typedef __bf16 V2 __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ pf_f32x16 mma(pf_u32x4 a, pf_u32x4 b, pf_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
+    const pf_f32x2 x = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
+  }
+};
+template <> struct PfMma<kF16> {
+  typedef _Float16 V8 __attribute__((ext_vector_type(8)));
+  typedef _Float16 V2 __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ pf_f32x16 mma(pf_u32x4 a, pf_u32x4 b, pf_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_f16_f32: round to nearest even
+    const pf_f32x2 x = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
+  }
+};
+
+struct PrefillArgs {
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  const int32_t* cu_q;      // [B + 1] or null (dense)
+  const int32_t* cu_k;
+  const int32_t* func;      // kPfFunc only
+  uint16_t* out;            // [B, Sq, Hq, D] / [total_q, Hq, D]
+  float* lse;               // [B, Hq, Sq] / [Hq, total_q], natural log
+  int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
+  int64_t f_sb, f_sh, f_sp, f_si;
+  int64_t total_q, total_k;
+  int B, Sq, Sk, Hq, G, nqt, n_func, skip;
+  float scale_log2;
+};
+
+struct PfExt { int pmax, pmin, lo, hi; };   // largest / smallest prefix of a group of rows, hull [lo, hi) of their bands (lo >= hi: none)
+
+__device__ __forceinline__ int pf_clamp(int64_t x, int hi) { return x < 0 ? 0 : (x > hi ? hi : (int)x); }
+__device__ __forceinline__ bool pf_hits(const PfExt& e, int n0, int n1) { return n0 < e.pmax || (e.lo < n1 && e.hi > n0); }
+
+template <int DT, int D, int MK>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
+  constexpr int KS = D + 8;          // K row stride in LDS (elements): rows stay 16-byte aligned
+  constexpr int VS = kPfKeys + 4;    // V^T row stride in LDS (elements): 34 dwords, the 32 rows of a half-wave hit 64 banks
+  constexpr int CH = D / 8;          // 16-byte chunks per row
+  __shared__ __attribute__((aligned(16))) uint16_t sK[kPfKeys * KS];
+  __shared__ __attribute__((aligned(16))) uint16_t sV[D * VS];
+  __shared__ int sExt[16];
+  using M = PfMma<DT>;
+
+  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
+  int64_t id = blockIdx.x;
+  const int hq = (int)(id % a.Hq); id /= a.Hq;
+  const int b = (int)(id % a.B);
+  const int qi = (int)(id / a.B);
+  const int qt = a.nqt - 1 - qi;   // late query tiles (the longest under a causal mask) first; heads fastest: a group shares K / V in L2
+  const int hk = hq / a.G;
+  const bool skip = a.skip != 0;
+
+  int64_t qrow0 = 0, krow0 = 0;
+  int Lq = a.Sq, Lk = a.Sk;
+  if (a.cu_q) {   // jagged: bounds clamped into the tensors and made monotone, so that no row outside them is ever read
+    int64_t s = a.cu_q[b], e = a.cu_q[b + 1];
+    s = s < 0 ? 0 : (s > a.total_q ? a.total_q : s);
+    e = e < s ? s : (e > a.total_q ? a.total_q : e);
+    qrow0 = s; Lq = (int)(e - s);
+    s = a.cu_k[b]; e = a.cu_k[b + 1];
+    s = s < 0 ? 0 : (s > a.total_k ? a.total_k : s);
+    e = e < s ? s : (e > a.total_k ? a.total_k : e);
+    krow0 = s; Lk = (int)(e - s);
+  }
+  if (qt * kPfRows >= Lq) return;   // (block-uniform: no barrier has been passed)
+
+  const int i = qt * kPfRows + wv * 32 + r;   // query row of this lane inside its sequence
+  const bool valid = i < Lq;
+  const int32_t* frow = nullptr;
+  if constexpr (MK == kPfFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
+
+  // ---- the row's extents, the wave's, the workgroup's
+  int pre = 0;
+  PfExt we{0, 0, kPfIntMax, 0};
+  if (valid) {
+    if constexpr (MK == kPfNone) pre = Lk;
+    if constexpr (MK == kPfCausal) pre = pf_clamp((int64_t)i + 1 + Lk - Lq, Lk);
+    if constexpr (MK == kPfFunc) {
+      pre = pf_clamp(frow[0], Lk);
+      for (int p = 1; p + 1 < a.n_func; p += 2) {
+        const int lo = pf_clamp(frow[(int64_t)p * a.f_sp], Lk), up = pf_clamp(frow[(int64_t)(p + 1) * a.f_sp], Lk);
+        if (lo < up) { we.lo = lo < we.lo ? lo : we.lo; we.hi = up > we.hi ? up : we.hi; }
+      }
+    }
+  }
+  we.pmax = pre; we.pmin = pre;   // (a row past the sequence end sees nothing: the wave then tests every tile it computes)
+#pragma unroll
+  for (int off = 1; off < 32; off <<= 1) {
+    const int x0 = __shfl_xor(we.pmax, off, 64), x1 = __shfl_xor(we.pmin, off, 64);
+    const int x2 = __shfl_xor(we.lo, off, 64), x3 = __shfl_xor(we.hi, off, 64);
+    we.pmax = x0 > we.pmax ? x0 : we.pmax; we.pmin = x1 < we.pmin ? x1 : we.pmin;
+    we.lo = x2 < we.lo ? x2 : we.lo; we.hi = x3 > we.hi ? x3 : we.hi;
+  }
+  if (lane == 0) { sExt[4 * wv] = we.pmax; sExt[4 * wv + 1] = we.pmin; sExt[4 * wv + 2] = we.lo; sExt[4 * wv + 3] = we.hi; }
+  __syncthreads();
+  PfExt be[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    be[w].pmax = __builtin_amdgcn_readfirstlane(sExt[4 * w]);
+    be[w].pmin = __builtin_amdgcn_readfirstlane(sExt[4 * w + 1]);
+    be[w].lo = __builtin_amdgcn_readfirstlane(sExt[4 * w + 2]);
+    be[w].hi = __builtin_amdgcn_readfirstlane(sExt[4 * w + 3]);
+  }
+  we.pmax = __builtin_amdgcn_readfirstlane(we.pmax); we.pmin = __builtin_amdgcn_readfirstlane(we.pmin);
+  we.lo = __builtin_amdgcn_readfirstlane(we.lo); we.hi = __builtin_amdgcn_readfirstlane(we.hi);
+
+  const int nt = (Lk + kPfKeys - 1) / kPfKeys;
+  // first tile at or after t that some wave reaches (nt: none)
+  auto next_tile = [&](int t) {
+    if (!skip) return t < nt ? t : nt;
+    for (; t < nt; ++t) {
+      const int n0 = t * kPfKeys, n1 = n0 + kPfKeys;
+      if (pf_hits(be[0], n0, n1) || pf_hits(be[1], n0, n1) || pf_hits(be[2], n0, n1) || pf_hits(be[3], n0, n1)) break;
+    }
+    return t;
+  };
+
+  pf_u32x4 qf[D / 16];
+  {
+    const uint16_t* qp = a.q + (int64_t)b * a.q_sb + (qrow0 + i) * a.q_ss + (int64_t)hq * a.q_sh + 8 * h;
+#pragma unroll
+    for (int s = 0; s < D / 16; ++s) {
+      pf_u32x4 z = {0u, 0u, 0u, 0u};
+      qf[s] = valid ? *reinterpret_cast<const pf_u32x4*>(qp + 16 * s) : z;
+    }
+  }
+
+  pf_f32x16 o[D / 32];
+#pragma unroll
+  for (int ii = 0; ii < D / 32; ++ii)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) o[ii][j] = 0.f;
+  float m = -INFINITY, lsum = 0.f;
+
+  const uint16_t* kb = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + krow0 * a.k_ss;
+  const uint16_t* vb = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh + krow0 * a.v_ss;
+
+  // Register staging, one tile ahead (as beam_ctx_kernel): keys at or past Lk are never read, they enter LDS as zeros.
+  constexpr int NK = kPfKeys * CH / 256, NV = 32 * CH / 256;
+  pf_u32x4 kreg[NK], vreg[NV][2];
+  auto load_tile = [&](int t) {
+    const int nv = Lk - t * kPfKeys;
+#pragma unroll
+    for (int ii = 0; ii < NK; ++ii) {
+      const int u = tid + 256 * ii, key = u / CH, c = u % CH;
+      pf_u32x4 val = {0u, 0u, 0u, 0u};
+      if (key < nv) val = *reinterpret_cast<const pf_u32x4*>(kb + (int64_t)(t * kPfKeys + key) * a.k_ss + 8 * c);
+      kreg[ii] = val;
+    }
+#pragma unroll
+    for (int ii = 0; ii < NV; ++ii) {
+      const int u = tid + 256 * ii, p = u & 31, c = u >> 5;
+      pf_u32x4 va = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
+      if (2 * p < nv) va = *reinterpret_cast<const pf_u32x4*>(vb + (int64_t)(t * kPfKeys + 2 * p) * a.v_ss + 8 * c);
+      if (2 * p + 1 < nv) vc = *reinterpret_cast<const pf_u32x4*>(vb + (int64_t)(t * kPfKeys + 2 * p + 1) * a.v_ss + 8 * c);
+      vreg[ii][0] = va; vreg[ii][1] = vc;
+    }
+  };
+
+  int t = next_tile(0);
+  if (t < nt) load_tile(t);
+  while (t < nt) {
+    const int n0 = t * kPfKeys, n1 = n0 + kPfKeys;
+    __syncthreads();
+#pragma unroll
+    for (int ii = 0; ii < NK; ++ii) {
+      const int u = tid + 256 * ii, key = u / CH, c = u % CH;
+      *reinterpret_cast<pf_u32x4*>(sK + key * KS + 8 * c) = kreg[ii];
+    }
+#pragma unroll
+    for (int ii = 0; ii < NV; ++ii) {   // V transposed: 8 dwords [d][2p, 2p + 1] per chunk pair
+      const int u = tid + 256 * ii, p = u & 31, c = u >> 5;
+      const pf_u32x4 va = vreg[ii][0], vc = vreg[ii][1];
+      uint32_t* dst = reinterpret_cast<uint32_t*>(sV + (8 * c) * VS + 2 * p);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        dst[(2 * e) * (VS / 2)] = (va[e] & 0xffffu) | (vc[e] << 16);
+        dst[(2 * e + 1) * (VS / 2)] = (va[e] >> 16) | (vc[e] & 0xffff0000u);
+      }
+    }
+    __syncthreads();
+    const int tn = next_tile(t + 1);
+    if (tn < nt) load_tile(tn);
+
+    if (!skip || pf_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
+      // S^T = K Q^T for the two 32-key sub-blocks
+      pf_f32x16 s0, s1;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+#pragma unroll
+      for (int s = 0; s < D / 16; ++s) {
+        const pf_u32x4 k0 = *reinterpret_cast<const pf_u32x4*>(sK + r * KS + 16 * s + 8 * h);
+        const pf_u32x4 k1 = *reinterpret_cast<const pf_u32x4*>(sK + (32 + r) * KS + 16 * s + 8 * h);
+        s0 = M::mma(k0, qf[s], s0);
+        s1 = M::mma(k1, qf[s], s1);
+      }
+      float p[32];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { p[j] = s0[j] * a.scale_log2; p[16 + j] = s1[j] * a.scale_log2; }
+      if (!skip || n1 > we.pmin) {   // some row of the wave does not see the whole tile through its prefix
+        uint32_t ok = 0;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+          const int key = n0 + 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h;
+          ok |= (uint32_t)(key < pre) << j;
+        }
+        if constexpr (MK == kPfFunc) {
+          if (!skip || (we.lo < n1 && we.hi > n0)) {
+            for (int pp = 1; pp + 1 < a.n_func; pp += 2) {
+              int lo = 0, up = 0;
+              if (valid) { lo = pf_clamp(frow[(int64_t)pp * a.f_sp], Lk); up = pf_clamp(frow[(int64_t)(pp + 1) * a.f_sp], Lk); }
+#pragma unroll
+              for (int j = 0; j < 32; ++j) {
+                const int key = n0 + 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h;
+                ok |= (uint32_t)((lo <= key) & (key < up)) << j;
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 32; ++j) p[j] = ((ok >> j) & 1u) ? p[j] : -INFINITY;
+      }
+      float mx = p[0];
+#pragma unroll
+      for (int j = 1; j < 32; ++j) mx = fmaxf(mx, p[j]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m, mx);
+      const float m_use = m_new == -INFINITY ? 0.f : m_new;   // a row that has seen no key yet: P = exp2(-inf - 0) = 0, not NaN
+      const float alpha = __builtin_amdgcn_exp2f(m - m_use);
+      m = m_new;
+      float ts = 0.f;
+#pragma unroll
+      for (int j = 0; j < 32; ++j) { p[j] = __builtin_amdgcn_exp2f(p[j] - m_use); ts += p[j]; }
+      lsum = lsum * alpha + ts;
+#pragma unroll
+      for (int ii = 0; ii < D / 32; ++ii)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) o[ii][j] *= alpha;
+
+      // O^T += V^T P^T
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {   // k-step: sub-block ks >> 1, step ks & 1: registers 8 ks .. 8 ks + 7 of p
+        pf_u32x4 pf;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pf[e] = M::pack2(p[8 * ks + 2 * e], p[8 * ks + 2 * e + 1]);
+#pragma unroll
+        for (int ii = 0; ii < D / 32; ++ii) {
+          const uint16_t* vp = sV + (32 * ii + r) * VS + 16 * ks + 4 * h;
+          const pf_u32x2 lo = *reinterpret_cast<const pf_u32x2*>(vp);
+          const pf_u32x2 hi = *reinterpret_cast<const pf_u32x2*>(vp + 8);
+          const pf_u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
+          o[ii] = M::mma(vf, pf, o[ii]);
+        }
+      }
+    }
+    t = tn;
+  }
+
+  const float l = lsum + __shfl_xor(lsum, 32, 64);
+  const float inv = l > 0.f ? 1.0f / l : 0.f;   // a row with no visible key: out = 0, lse = -inf
+  if (valid) {
+    const int64_t orow = (a.cu_q ? qrow0 : (int64_t)b * a.Sq) + i;
+    uint16_t* op = a.out + (orow * a.Hq + hq) * D + 4 * h;
+#pragma unroll
+    for (int ii = 0; ii < D / 32; ++ii)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        pf_u32x2 x;
+        x[0] = M::pack2(o[ii][4 * g] * inv, o[ii][4 * g + 1] * inv);
+        x[1] = M::pack2(o[ii][4 * g + 2] * inv, o[ii][4 * g + 3] * inv);
+        *reinterpret_cast<pf_u32x2*>(op + 32 * ii + 8 * g) = x;
+      }
+    if (h == 0) {
+      const int64_t li = a.cu_q ? (int64_t)hq * a.total_q + qrow0 + i : ((int64_t)b * a.Hq + hq) * a.Sq + i;
+      a.lse[li] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kPfLn2 : -INFINITY;   // v_log_f32 is log2
+    }
+  }
+}
+
+static inline bool pf_aligned(const void* p, int64_t s0, int64_t s1, int64_t s2) {
+  return ((uintptr_t)p % 16 == 0) && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
+}
+
+template <int DT, int D>
+static void pf_launch(int mask, dim3 grid, hipStream_t stream, const PrefillArgs& c) {
+  const dim3 block(256);
+  if (mask == kPfNone) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfNone>), grid, block, 0, stream, c);
+  else if (mask == kPfCausal) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfCausal>), grid, block, 0, stream, c);
+  else hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfFunc>), grid, block, 0, stream, c);
+}
+
+}  // namespace mi355
+
+using namespace mi355;
+
+int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, const void* k,
+                       int64_t k_stride_b, int64_t k_stride_s, int64_t k_stride_h, const void* v, int64_t v_stride_b,
+                       int64_t v_stride_s, int64_t v_stride_h, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                       int64_t B, int64_t Sq, int64_t Sk, int64_t total_q, int64_t total_k, int64_t Hq, int64_t Hkv, int64_t D,
+                       int mask, const int32_t* func, int64_t n_func, int64_t func_heads, int64_t func_stride_b,
+                       int64_t func_stride_h, int64_t func_stride_f, int64_t func_stride_s, float softmax_scale,
+                       int skip_tiles, void* out, float* lse, int dtype, hipStream_t stream) {
+  MI355_CHECK_ARG(dtype == kBF16 || dtype == kF16, "prefill_attn: dtype must be bf16 or fp16");
+  MI355_CHECK_ARG(D == 64 || D == 128, "prefill_attn: head dim must be 64 or 128");
+  MI355_CHECK_ARG(B >= 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "prefill_attn: Hq must be a multiple of Hkv");
+  MI355_CHECK_ARG(Sq >= 0 && Sk >= 0 && total_q >= 0 && total_k >= 0, "prefill_attn: negative length");
+  MI355_CHECK_ARG(mask == kPfNone || mask == kPfCausal || mask == kPfFunc,
+                  "prefill_attn: mask must be 0 (none), 1 (causal) or 2 (arbitrary func)");
+  MI355_CHECK_ARG((cu_seqlens_q == nullptr) == (cu_seqlens_k == nullptr),
+                  "prefill_attn: cu_seqlens_q and cu_seqlens_k come together (jagged) or not at all (dense)");
+  const bool jagged = cu_seqlens_q != nullptr;
+  if (mask == kPfFunc) {
+    MI355_CHECK_ARG(!jagged, "prefill_attn: the arbitrary func mask applies to the dense form only (no cu_seqlens)");
+    MI355_CHECK_ARG(n_func >= 1 && n_func % 2 == 1, "prefill_attn: n_func must be odd and >= 1");
+    MI355_CHECK_ARG(func_heads == 1 || func_heads == Hq, "prefill_attn: func must have 1 or Hq heads");
+    MI355_CHECK_ARG(n_func <= INT32_MAX, "prefill_attn: n_func does not fit 31 bits");
+  } else {
+    MI355_CHECK_ARG(func == nullptr, "prefill_attn: func is given but the mask kind is not 2 (a causal or plain call takes none)");
+  }
+  MI355_CHECK_ARG(skip_tiles == 0 || skip_tiles == 1, "prefill_attn: skip_tiles must be 0 or 1");
+  MI355_CHECK_ARG(B <= INT32_MAX && Hq <= INT32_MAX && Sq <= INT32_MAX - kPfRows && Sk <= INT32_MAX - kPfKeys &&
+                      total_q <= INT32_MAX - kPfRows && total_k <= INT32_MAX - kPfKeys,
+                  "prefill_attn: a dimension does not fit 31 bits");
+  const int64_t rows = jagged ? total_q : B * Sq;
+  if (B == 0 || rows == 0 || Sq == 0) return MI355_OK;
+  MI355_CHECK_ARG(q && out && lse, "prefill_attn: null pointer");
+  MI355_CHECK_ARG(pf_aligned(q, q_stride_b, q_stride_s, q_stride_h) && (uintptr_t)out % 16 == 0,
+                  "prefill_attn: q and out need 16-byte aligned rows (base aligned, strides multiples of 8 elements)");
+  if (jagged ? total_k > 0 : Sk > 0) {
+    MI355_CHECK_ARG(k && v, "prefill_attn: null k / v pointer");
+    MI355_CHECK_ARG(pf_aligned(k, k_stride_b, k_stride_s, k_stride_h) && pf_aligned(v, v_stride_b, v_stride_s, v_stride_h),
+                    "prefill_attn: k / v rows need 16-byte alignment (base aligned, strides multiples of 8 elements)");
+  }
+  if (mask == kPfFunc) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "prefill_attn: func is null or misaligned");
+  const int64_t nqt = ceil_div(Sq, (int64_t)kPfRows);   // jagged: Sq is max_seqlen_q
+  const int64_t nblocks = nqt * B * Hq;
+  MI355_CHECK_ARG(nblocks <= INT32_MAX, "prefill_attn: launch too large");
+
+  PrefillArgs c;
+  c.q = (const uint16_t*)q; c.k = (const uint16_t*)k; c.v = (const uint16_t*)v;
+  c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.func = func; c.out = (uint16_t*)out; c.lse = lse;
+  c.q_sb = jagged ? 0 : q_stride_b; c.q_ss = q_stride_s; c.q_sh = q_stride_h;
+  c.k_sb = jagged ? 0 : k_stride_b; c.k_ss = k_stride_s; c.k_sh = k_stride_h;
+  c.v_sb = jagged ? 0 : v_stride_b; c.v_ss = v_stride_s; c.v_sh = v_stride_h;
+  c.f_sb = func_stride_b; c.f_sh = func_heads == 1 ? 0 : func_stride_h; c.f_sp = func_stride_f; c.f_si = func_stride_s;
+  c.total_q = total_q; c.total_k = total_k;
+  c.B = (int)B; c.Sq = (int)Sq; c.Sk = (int)Sk; c.Hq = (int)Hq; c.G = (int)(Hq / Hkv); c.nqt = (int)nqt;
+  c.n_func = (int)n_func; c.skip = skip_tiles;
+  c.scale_log2 = softmax_scale * kPfLog2e;
+  const dim3 grid((unsigned)nblocks);
+  if (dtype == kBF16) {
+    if (D == 64) pf_launch<kBF16, 64>(mask, grid, stream, c);
+    else pf_launch<kBF16, 128>(mask, grid, stream, c);
+  } else {
+    if (D == 64) pf_launch<kF16, 64>(mask, grid, stream, c);
+    else pf_launch<kF16, 128>(mask, grid, stream, c);
+  }
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
+}

@@ -252,6 +252,10 @@ _SIGS = {
                                c_p, c_int, c_i64, c_i64, c_i64, c_i64,  # top-k indices
                                c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_i64,  # B, W, Hq, Hkv, D, decode_nums, scale, splits
                                c_p, c_p, c_int, c_p, c_i64, c_p],
+    "mi355_prefill_attn": [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64,  # q, k, v + strides
+                           c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # cu_q, cu_k, B, Sq, Sk, totals, Hq, Hkv, D
+                           c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # mask, func, n_func, heads, strides
+                           c_f, c_int, c_p, c_p, c_int, c_p],  # scale, skip_tiles, out, lse, dtype, stream
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
