@@ -22,9 +22,10 @@ from typing import Optional, Tuple
 import torch
 
 import mi355_native as N
+from mi355_native import rows_aligned as _rows_aligned
 
-KEY_TILE = 64      # keys per tile of the context kernel (csrc/beam_decode.hip: kBdKeys)
-ROW_TILE = 128     # packed query rows (beam x group head) per workgroup (kBdRows)
+KEY_TILE = 64      # keys per tile of the context kernel (csrc/softmax_tile_dev.h: kSmKeys)
+ROW_TILE = 128     # packed query rows (beam x group head) per workgroup (kSmRows)
 NUM_CUS = 256
 # Split rule, read off the _num_splits sweep of profiles/beam_decode_bench.txt: split until the launch has as many
 # workgroups as the CUs hold at once (the context kernel runs one workgroup per CU at D = 128, where a wave takes 247 VGPRs,
@@ -117,15 +118,6 @@ def _require_gpu(**tensors):
     for name, t in tensors.items():
         if t is not None and not t.is_cuda:
             raise BeamDecodeError(f"{name} must be a GPU tensor (there is no CPU path), got device {t.device}")
-
-
-def _rows_aligned(t: torch.Tensor) -> torch.Tensor:
-    """The kernels read rows in 16-byte pieces: a view whose strides or base are not multiples of 8 elements is copied."""
-    if t.numel() == 0:
-        return t
-    if t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]):
-        return t
-    return t.contiguous()
 
 
 def _forward(q, k_context, v_context, k_beam, v_beam, topk_indices, decode_nums, softmax_scale, seqused_k, cu_seqlens_k,

@@ -6,62 +6,24 @@
 //
 // Two launches per call, no float atomics, bitwise reproducible for a given split count:
 //
-// 1. beam_ctx_kernel: flash-decoding on v_mfma_f32_32x32x16_{bf16,f16}.  One workgroup (4 waves) owns one (batch, kv head,
-//    tile of 128 packed query rows, KV split).  The packed row of beam w and group head g is w G + g, so the K / V tile of a
-//    kv head serves all W G rows of its group.  A wave owns 32 rows; its Q fragments stay in registers.  Per tile of 64 keys:
-//      * K goes to LDS as [key][D + 8], V transposed as [d][64 + 4] (two keys per 32-bit write: conflict-free);
-//      * S^T = K Q^T: the key index lies in the accumulator registers and the query on the lane, so a row's max and sum are
-//        per-lane reductions over registers plus one exchange between the two lane halves;
-//      * P (rounded once to the operand type; the row sum is taken from the fp32 P) is the B operand of O^T += V^T P^T with
-//        no trip through LDS: element j of k-step s of lane half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3) of the 32-key
-//        sub-block, and the V^T fragment is read in that same order.
-//    Running max and sum are fp32, in log2 units (scores are pre-scaled by softmax_scale log2 e, v_exp_f32).  A split is a
-//    range of the sample's OWN key tiles (seqused_k and jagged contexts included), tiles [s nt / ns, (s + 1) nt / ns); a
-//    split with no tile writes lse = -inf and nothing else.  Every split writes a normalised fp32 partial O and its LSE.
+// 1. beam_ctx_kernel: flash-decoding on the shared key-tile core of softmax_tile_dev.h (LDS layout, register-to-key mapping,
+//    online softmax and P V are described there).  One workgroup (4 waves) owns one (batch, kv head, tile of 128 packed query
+//    rows, KV split).  The packed row of beam w and group head g is w G + g, so the K / V tile of a kv head serves all W G
+//    rows of its group.  A split is a range of the sample's OWN key tiles (seqused_k and jagged contexts included), tiles
+//    [s nt / ns, (s + 1) nt / ns); a split with no tile writes lse = -inf and nothing else.  Every split writes a normalised
+//    fp32 partial O and its LSE (log2 units).  Only the last tile of a sequence is masked (key >= nvalid), and key 0 of every
+//    tile exists, so the running max is always finite.
 //
 // 2. beam_merge_kernel: 16 lanes per row (b, w, h).  Gathers the decode_nums beam rows through the index list, scores and
 //    softmax in fp32 on the vector ALU (online), then folds in the ns context partials by log-sum-exp and writes `out` in
 //    the dtype of q and `lse` in fp32.  An index outside [0, decode_nums W) is never dereferenced: that key is absent.
 #include "common.h"
+#include "softmax_tile_dev.h"
 #include "../../include/recsys_amd.h"
 
 #include <math.h>
 
 namespace mi355 {
-
-typedef float bd_f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t bd_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t bd_u32x2 __attribute__((ext_vector_type(2)));
-typedef float bd_f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kBdKeys = 64;     // keys per tile
-constexpr int kBdRows = 128;    // packed query rows per workgroup (4 waves x 32)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-
-template <int DT> struct BdMma;
-template <> struct BdMma<kBF16> {
-  typedef __bf16 V8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 V2 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ bd_f32x16 mma(bd_u32x4 a, bd_u32x4 b, bd_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
-    const bd_f32x2 x = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
-  }
-};
-template <> struct BdMma<kF16> {
-  typedef _Float16 V8 __attribute__((ext_vector_type(8)));
-  typedef _Float16 V2 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ bd_f32x16 mma(bd_u32x4 a, bd_u32x4 b, bd_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_f16_f32: round to nearest even
-    const bd_f32x2 x = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
-  }
-};
 
 struct BeamCtxArgs {
   const uint16_t* q;
@@ -80,12 +42,9 @@ struct BeamCtxArgs {
 
 template <int DT, int D>
 __global__ void __launch_bounds__(256) beam_ctx_kernel(BeamCtxArgs a) {
-  constexpr int KS = D + 8;          // K row stride in LDS (elements): rows stay 16-byte aligned
-  constexpr int VS = kBdKeys + 4;    // V^T row stride in LDS (elements): 34 dwords, the 32 rows of a half-wave hit 64 banks
-  constexpr int CH = D / 8;          // 16-byte chunks per row
-  __shared__ __attribute__((aligned(16))) uint16_t sK[kBdKeys * KS];
-  __shared__ __attribute__((aligned(16))) uint16_t sV[D * VS];
-  using M = BdMma<DT>;
+  using T = SmTile<DT, D>;
+  __shared__ __attribute__((aligned(16))) uint16_t sK[T::kSK];
+  __shared__ __attribute__((aligned(16))) uint16_t sV[T::kSV];
 
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
   int64_t id = blockIdx.x;
@@ -106,10 +65,10 @@ __global__ void __launch_bounds__(256) beam_ctx_kernel(BeamCtxArgs a) {
     const int u = a.seqused[b];
     len = u < 0 ? 0 : (u < a.Sk ? u : a.Sk);
   }
-  const int nt = (len + kBdKeys - 1) / kBdKeys;
+  const int nt = (len + kSmKeys - 1) / kSmKeys;
   const int t0 = (int)((int64_t)sp * nt / a.ns), t1 = (int)((int64_t)(sp + 1) * nt / a.ns);
 
-  const int rr = qt * kBdRows + wv * 32 + r;       // packed row of this lane
+  const int rr = qt * kSmRows + wv * 32 + r;       // packed row of this lane
   const bool valid = rr < a.W * a.G;
   const int w = valid ? rr / a.G : 0, hq = hk * a.G + (valid ? rr % a.G : 0);
   const int64_t prow = ((int64_t)b * a.W + w) * a.Hq + hq;
@@ -119,21 +78,10 @@ __global__ void __launch_bounds__(256) beam_ctx_kernel(BeamCtxArgs a) {
     return;
   }
 
-  bd_u32x4 qf[D / 16];
-  {
-    const uint16_t* qp = a.q + (int64_t)b * a.q_sb + (int64_t)w * a.q_sw + (int64_t)hq * a.q_sh + 8 * h;
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      bd_u32x4 z = {0u, 0u, 0u, 0u};
-      qf[s] = valid ? *reinterpret_cast<const bd_u32x4*>(qp + 16 * s) : z;
-    }
-  }
-
-  bd_f32x16 o[D / 32];
-#pragma unroll
-  for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) o[i][j] = 0.f;
+  sm_u32x4 qf[D / 16];
+  T::load_q(a.q + (int64_t)b * a.q_sb + (int64_t)w * a.q_sw + (int64_t)hq * a.q_sh + 8 * h, valid, qf);
+  sm_f32x16 o[D / 32];
+  T::zero_acc(o);
   float m = -INFINITY, lsum = 0.f;
 
   const uint16_t* kb = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + row0 * a.k_ss;
@@ -141,105 +89,28 @@ __global__ void __launch_bounds__(256) beam_ctx_kernel(BeamCtxArgs a) {
 
   // Register staging, one tile ahead: the global loads of tile t + 1 are issued before the MFMAs of tile t and written to
   // LDS after them, so that their latency lies under the compute of a workgroup that has its CU to itself.
-  constexpr int NK = kBdKeys * CH / 256, NV = 32 * CH / 256;
-  bd_u32x4 kreg[NK], vreg[NV][2];
-  auto load_tile = [&](int t) {
-    const int nv = len - t * kBdKeys;
-    // K: consecutive lanes take consecutive 16-byte chunks of a row
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-      const int u = tid + 256 * i, key = u / CH, c = u % CH;
-      bd_u32x4 val = {0u, 0u, 0u, 0u};
-      if (key < nv) val = *reinterpret_cast<const bd_u32x4*>(kb + (int64_t)(t * kBdKeys + key) * a.k_ss + 8 * c);
-      kreg[i] = val;
-    }
-    // V: a lane takes one chunk of keys 2p and 2p + 1
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int u = tid + 256 * i, p = u & 31, c = u >> 5;
-      bd_u32x4 va = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
-      if (2 * p < nv) va = *reinterpret_cast<const bd_u32x4*>(vb + (int64_t)(t * kBdKeys + 2 * p) * a.v_ss + 8 * c);
-      if (2 * p + 1 < nv) vc = *reinterpret_cast<const bd_u32x4*>(vb + (int64_t)(t * kBdKeys + 2 * p + 1) * a.v_ss + 8 * c);
-      vreg[i][0] = va; vreg[i][1] = vc;
-    }
-  };
+  typename T::Stage st;
+  auto load_tile = [&](int t) { T::load_tile(st, kb, vb, a.k_ss, a.v_ss, t, len, tid); };   // (only shortens the two calls)
   load_tile(t0);
 
   for (int t = t0; t < t1; ++t) {
-    const int nvalid = len - t * kBdKeys;   // >= 1
+    const int nvalid = len - t * kSmKeys;   // >= 1
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-      const int u = tid + 256 * i, key = u / CH, c = u % CH;
-      *reinterpret_cast<bd_u32x4*>(sK + key * KS + 8 * c) = kreg[i];
-    }
-    // V transposed: 8 dwords [d][2p, 2p + 1] per chunk pair
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int u = tid + 256 * i, p = u & 31, c = u >> 5;
-      const bd_u32x4 va = vreg[i][0], vc = vreg[i][1];
-      uint32_t* dst = reinterpret_cast<uint32_t*>(sV + (8 * c) * VS + 2 * p);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        dst[(2 * e) * (VS / 2)] = (va[e] & 0xffffu) | (vc[e] << 16);
-        dst[(2 * e + 1) * (VS / 2)] = (va[e] >> 16) | (vc[e] & 0xffff0000u);
-      }
-    }
+    T::store_tile(st, sK, sV, tid);
     __syncthreads();
     if (t + 1 < t1) load_tile(t + 1);
 
-    // S^T = K Q^T for the two 32-key sub-blocks
-    bd_f32x16 s0, s1;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      const bd_u32x4 k0 = *reinterpret_cast<const bd_u32x4*>(sK + r * KS + 16 * s + 8 * h);
-      const bd_u32x4 k1 = *reinterpret_cast<const bd_u32x4*>(sK + (32 + r) * KS + 16 * s + 8 * h);
-      s0 = M::mma(k0, qf[s], s0);
-      s1 = M::mma(k1, qf[s], s1);
-    }
     float p[32];
+    T::scores(sK, qf, a.scale_log2, r, h, p);
+    if (nvalid < kSmKeys) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) { p[j] = s0[j] * a.scale_log2; p[16 + j] = s1[j] * a.scale_log2; }
-    if (nvalid < kBdKeys) {
-#pragma unroll
-      for (int j = 0; j < 32; ++j) {
-        const int key = 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h;
-        if (key >= nvalid) p[j] = -INFINITY;
-      }
+      for (int j = 0; j < 32; ++j)
+        if (sm_key_of(j, h) >= nvalid) p[j] = -INFINITY;
     }
-    float mx = p[0];
+    const float alpha = T::template softmax_step<false>(p, m, lsum);   // m stays finite: key 0 of a tile always exists
 #pragma unroll
-    for (int j = 1; j < 32; ++j) mx = fmaxf(mx, p[j]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m, mx);          // finite: key 0 of a tile always exists
-    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-    m = m_new;
-    float ts = 0.f;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) { p[j] = __builtin_amdgcn_exp2f(p[j] - m_new); ts += p[j]; }
-    lsum = lsum * alpha + ts;
-#pragma unroll
-    for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) o[i][j] *= alpha;
-
-    // O^T += V^T P^T
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {   // k-step: sub-block ks >> 1, step ks & 1: registers 8 ks .. 8 ks + 7 of p
-      bd_u32x4 pf;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) pf[e] = M::pack2(p[8 * ks + 2 * e], p[8 * ks + 2 * e + 1]);
-#pragma unroll
-      for (int i = 0; i < D / 32; ++i) {
-        const uint16_t* vp = sV + (32 * i + r) * VS + 16 * ks + 4 * h;
-        const bd_u32x2 lo = *reinterpret_cast<const bd_u32x2*>(vp);
-        const bd_u32x2 hi = *reinterpret_cast<const bd_u32x2*>(vp + 8);
-        const bd_u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-        o[i] = M::mma(vf, pf, o[i]);
-      }
-    }
+    for (int i = 0; i < D / 32; ++i) o[i] *= alpha;
+    T::pv(sV, r, h, p, o);
   }
 
   const float l = lsum + __shfl_xor(lsum, 32, 64);
@@ -346,11 +217,7 @@ __global__ void __launch_bounds__(256) beam_merge_kernel(BeamMergeArgs a) {
     f.x = acc[4 * i] * inv; f.y = acc[4 * i + 1] * inv; f.z = acc[4 * i + 2] * inv; f.w = acc[4 * i + 3] * inv;
     st4<DT>(outp, 4 * i, f);
   }
-  if (sub == 0) a.lse[row] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kLn2 : -INFINITY;
-}
-
-static inline bool bd_aligned(const void* p, int64_t s0, int64_t s1, int64_t s2) {
-  return ((uintptr_t)p % 16 == 0) && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
+  if (sub == 0) a.lse[row] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kSmLn2 : -INFINITY;
 }
 
 }  // namespace mi355
@@ -383,34 +250,34 @@ int mi355_beam_decode_attn(const void* q, int64_t q_stride_b, int64_t q_stride_w
   const int64_t rows = B * W * Hq;
   if (rows == 0) return MI355_OK;
   const int64_t G = Hq / Hkv;
-  MI355_CHECK_ARG(B <= INT32_MAX && W * G <= INT32_MAX - kBdRows && Sk <= INT32_MAX - kBdKeys && Hq <= INT32_MAX &&
+  MI355_CHECK_ARG(B <= INT32_MAX && W * G <= INT32_MAX - kSmRows && Sk <= INT32_MAX - kSmKeys && Hq <= INT32_MAX &&
                       decode_nums <= INT32_MAX, "beam_decode_attn: a dimension does not fit 31 bits");
   MI355_CHECK_ARG(q && out && lse, "beam_decode_attn: null pointer");
-  MI355_CHECK_ARG(bd_aligned(q, q_stride_b, q_stride_w, q_stride_h) && (uintptr_t)out % 16 == 0,
+  MI355_CHECK_ARG(sm_aligned(q, q_stride_b, q_stride_w, q_stride_h) && (uintptr_t)out % 16 == 0,
                   "beam_decode_attn: q and out need 16-byte aligned rows");
   const bool has_ctx = cu_seqlens_k ? total_k > 0 : Sk > 0;
   if (has_ctx) {
     MI355_CHECK_ARG(k_context && v_context, "beam_decode_attn: null context pointer");
-    MI355_CHECK_ARG(bd_aligned(k_context, kc_stride_b, kc_stride_s, kc_stride_h) &&
-                        bd_aligned(v_context, vc_stride_b, vc_stride_s, vc_stride_h),
+    MI355_CHECK_ARG(sm_aligned(k_context, kc_stride_b, kc_stride_s, kc_stride_h) &&
+                        sm_aligned(v_context, vc_stride_b, vc_stride_s, vc_stride_h),
                     "beam_decode_attn: context rows need 16-byte alignment (strides multiples of 8 elements)");
   }
   if (decode_nums > 0) {
     MI355_CHECK_ARG(k_beam && v_beam && topk_indices, "beam_decode_attn: null beam pointer");
-    MI355_CHECK_ARG(bd_aligned(k_beam, kb_stride_b, kb_stride_s, kb_stride_h) &&
-                        bd_aligned(v_beam, vb_stride_b, vb_stride_s, vb_stride_h),
+    MI355_CHECK_ARG(sm_aligned(k_beam, kb_stride_b, kb_stride_s, kb_stride_h) &&
+                        sm_aligned(v_beam, vb_stride_b, vb_stride_s, vb_stride_h),
                     "beam_decode_attn: beam rows need 16-byte alignment (strides multiples of 8 elements)");
   }
   MI355_CHECK_ARG(workspace && (uintptr_t)workspace % 16 == 0 &&
                       workspace_bytes >= mi355_beam_decode_workspace_bytes(B, W, Hq, D, num_splits),
                   "beam_decode_attn: workspace missing, misaligned or too small");
-  const int64_t nqt = ceil_div(W * G, (int64_t)kBdRows);
+  const int64_t nqt = ceil_div(W * G, (int64_t)kSmRows);
   const int64_t nblocks = nqt * num_splits * Hkv * B;
   MI355_CHECK_ARG(nblocks <= INT32_MAX && ceil_div(rows, (int64_t)16) <= INT32_MAX, "beam_decode_attn: launch too large");
 
   float* o_part = reinterpret_cast<float*>(workspace);
   float* lse_part = o_part + num_splits * rows * D;
-  const float scale_log2 = softmax_scale * kLog2e;
+  const float scale_log2 = softmax_scale * kSmLog2e;
 
   BeamCtxArgs c;
   c.q = (const uint16_t*)q; c.k = (const uint16_t*)k_context; c.v = (const uint16_t*)v_context;

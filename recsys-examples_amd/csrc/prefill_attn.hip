@@ -8,13 +8,16 @@
 // for gfx950 from the semantics (bottom-right aligned causal as in flash-attn >= 2.1; the interval encoding of arbitrary_func,
 // examples/sid_gr/model/attention_mask.py:210-275, which is the `func` of hstu_attn.hip).
 //
-// One launch, no workspace, no atomics: bitwise reproducible.  prefill_attn_kernel has the structure of beam_ctx_kernel:
-// v_mfma_f32_32x32x16_{bf16,f16}; one workgroup (4 waves) owns one (sequence, query head, tile of 128 query rows), a wave 32
-// rows, its Q fragments in registers; K / V come from kv head h / G.  Per tile of 64 keys K goes to LDS as [key][D + 8] and V
-// transposed as [d][64 + 4]; S^T = K Q^T puts the key index in the accumulator registers and the query row on the lane, so a
-// row's max and sum are per-lane reductions plus one exchange between the lane halves; P, rounded once to the operand type
-// (the row sum takes the fp32 P), is the B operand of O^T += V^T P^T with no trip through LDS.  Running max and sum are fp32 in
-// log2 units.  The global loads of the next tile are issued before the MFMAs of this one and written to LDS after them.
+// One launch, no workspace, no atomics: bitwise reproducible.  prefill_attn_kernel has the tile loop of beam_ctx_kernel, whose
+// pieces are SmTile of softmax_tile_dev.h (LDS layout, register-to-key mapping, online softmax and P V are described there):
+// one workgroup (4 waves) owns one (sequence, query head, tile of 128 query rows); K / V come from kv head h / G; the global
+// loads of the next tile are issued before the MFMAs of this one and written to LDS after them.  From the header this kernel
+// takes the types, the constants, SmMma, sm_key_of and SmTile::scores; the Q load, the K / V staging, the softmax step and
+// the P V loop are WRITTEN OUT below, equal line for line to SmTile's.  Measured reason: the arbitrary-mask instantiations
+// are at the SGPR limit and the D = 64 ones close to it in scheduling; with any of those pieces taken from SmTile the
+// compiler placed scalar spill reloads and the schedule differently, and some shape lost 0.5 - 3 % (arbitrary mask with
+// skip_tiles = 0, or dense D = 64 at S = 8192).  As it stands the kernel compiles to the instructions it had before the
+// header existed.  A change to one of these pieces in the header has to be made here as well.
 //
 // Masks.  Every query row has a prefix bound `pre` (keys j < pre are seen) and, for the arbitrary kind, bands [lo, up):
 //   none     pre = Lk
@@ -29,47 +32,15 @@
 // A row with no visible key -- in a tile (m stays -inf: the exponent is taken against 0, so P = exp2(-inf) = 0 and no
 // inf - inf arises) or at all (l = 0: out = 0, lse = -inf).
 #include "common.h"
+#include "softmax_tile_dev.h"
 #include "../../include/recsys_amd.h"
 
 #include <math.h>
 
 namespace mi355 {
 
-typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t pf_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t pf_u32x2 __attribute__((ext_vector_type(2)));
-typedef float pf_f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kPfKeys = 64;     // keys per tile
-constexpr int kPfRows = 128;    // query rows per workgroup (4 waves x 32)
-constexpr float kPfLog2e = 1.4426950408889634f;
-constexpr float kPfLn2 = 0.6931471805599453f;
 constexpr int kPfNone = 0, kPfCausal = 1, kPfFunc = 2;
 constexpr int kPfIntMax = 0x7fffffff;
-
-template <int DT> struct PfMma;
-template <> struct PfMma<kBF16> {
-  typedef __bf16 V8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 V2 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ pf_f32x16 mma(pf_u32x4 a, pf_u32x4 b, pf_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_bf16_f32: round to nearest even
-    const pf_f32x2 x = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
-  }
-};
-template <> struct PfMma<kF16> {
-  typedef _Float16 V8 __attribute__((ext_vector_type(8)));
-  typedef _Float16 V2 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ pf_f32x16 mma(pf_u32x4 a, pf_u32x4 b, pf_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_f16_f32: round to nearest even
-    const pf_f32x2 x = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, V2));
-  }
-};
 
 struct PrefillArgs {
   const uint16_t* q;
@@ -94,13 +65,14 @@ __device__ __forceinline__ bool pf_hits(const PfExt& e, int n0, int n1) { return
 
 template <int DT, int D, int MK>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
-  constexpr int KS = D + 8;          // K row stride in LDS (elements): rows stay 16-byte aligned
-  constexpr int VS = kPfKeys + 4;    // V^T row stride in LDS (elements): 34 dwords, the 32 rows of a half-wave hit 64 banks
+  constexpr int KS = D + 8;          // = SmTile::KS
+  constexpr int VS = kSmKeys + 4;    // = SmTile::VS
   constexpr int CH = D / 8;          // 16-byte chunks per row
-  __shared__ __attribute__((aligned(16))) uint16_t sK[kPfKeys * KS];
+  __shared__ __attribute__((aligned(16))) uint16_t sK[kSmKeys * KS];
   __shared__ __attribute__((aligned(16))) uint16_t sV[D * VS];
   __shared__ int sExt[16];
-  using M = PfMma<DT>;
+  using M = SmMma<DT>;
+  using T = SmTile<DT, D>;
 
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
   int64_t id = blockIdx.x;
@@ -123,9 +95,9 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
     e = e < s ? s : (e > a.total_k ? a.total_k : e);
     krow0 = s; Lk = (int)(e - s);
   }
-  if (qt * kPfRows >= Lq) return;   // (block-uniform: no barrier has been passed)
+  if (qt * kSmRows >= Lq) return;   // (block-uniform: no barrier has been passed)
 
-  const int i = qt * kPfRows + wv * 32 + r;   // query row of this lane inside its sequence
+  const int i = qt * kSmRows + wv * 32 + r;   // query row of this lane inside its sequence
   const bool valid = i < Lq;
   const int32_t* frow = nullptr;
   if constexpr (MK == kPfFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
@@ -165,28 +137,28 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
   we.pmax = __builtin_amdgcn_readfirstlane(we.pmax); we.pmin = __builtin_amdgcn_readfirstlane(we.pmin);
   we.lo = __builtin_amdgcn_readfirstlane(we.lo); we.hi = __builtin_amdgcn_readfirstlane(we.hi);
 
-  const int nt = (Lk + kPfKeys - 1) / kPfKeys;
+  const int nt = (Lk + kSmKeys - 1) / kSmKeys;
   // first tile at or after t that some wave reaches (nt: none)
   auto next_tile = [&](int t) {
     if (!skip) return t < nt ? t : nt;
     for (; t < nt; ++t) {
-      const int n0 = t * kPfKeys, n1 = n0 + kPfKeys;
+      const int n0 = t * kSmKeys, n1 = n0 + kSmKeys;
       if (pf_hits(be[0], n0, n1) || pf_hits(be[1], n0, n1) || pf_hits(be[2], n0, n1) || pf_hits(be[3], n0, n1)) break;
     }
     return t;
   };
 
-  pf_u32x4 qf[D / 16];
+  sm_u32x4 qf[D / 16];
   {
     const uint16_t* qp = a.q + (int64_t)b * a.q_sb + (qrow0 + i) * a.q_ss + (int64_t)hq * a.q_sh + 8 * h;
 #pragma unroll
     for (int s = 0; s < D / 16; ++s) {
-      pf_u32x4 z = {0u, 0u, 0u, 0u};
-      qf[s] = valid ? *reinterpret_cast<const pf_u32x4*>(qp + 16 * s) : z;
+      sm_u32x4 z = {0u, 0u, 0u, 0u};
+      qf[s] = valid ? *reinterpret_cast<const sm_u32x4*>(qp + 16 * s) : z;
     }
   }
 
-  pf_f32x16 o[D / 32];
+  sm_f32x16 o[D / 32];
 #pragma unroll
   for (int ii = 0; ii < D / 32; ++ii)
 #pragma unroll
@@ -196,24 +168,24 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
   const uint16_t* kb = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + krow0 * a.k_ss;
   const uint16_t* vb = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh + krow0 * a.v_ss;
 
-  // Register staging, one tile ahead (as beam_ctx_kernel): keys at or past Lk are never read, they enter LDS as zeros.
-  constexpr int NK = kPfKeys * CH / 256, NV = 32 * CH / 256;
-  pf_u32x4 kreg[NK], vreg[NV][2];
+  // Register staging, one tile ahead (SmTile::load_tile / store_tile, written out): keys at or past Lk enter LDS as zeros.
+  constexpr int NK = kSmKeys * CH / 256, NV = 32 * CH / 256;
+  sm_u32x4 kreg[NK], vreg[NV][2];
   auto load_tile = [&](int t) {
-    const int nv = Lk - t * kPfKeys;
+    const int nv = Lk - t * kSmKeys;
 #pragma unroll
     for (int ii = 0; ii < NK; ++ii) {
       const int u = tid + 256 * ii, key = u / CH, c = u % CH;
-      pf_u32x4 val = {0u, 0u, 0u, 0u};
-      if (key < nv) val = *reinterpret_cast<const pf_u32x4*>(kb + (int64_t)(t * kPfKeys + key) * a.k_ss + 8 * c);
+      sm_u32x4 val = {0u, 0u, 0u, 0u};
+      if (key < nv) val = *reinterpret_cast<const sm_u32x4*>(kb + (int64_t)(t * kSmKeys + key) * a.k_ss + 8 * c);
       kreg[ii] = val;
     }
 #pragma unroll
     for (int ii = 0; ii < NV; ++ii) {
       const int u = tid + 256 * ii, p = u & 31, c = u >> 5;
-      pf_u32x4 va = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
-      if (2 * p < nv) va = *reinterpret_cast<const pf_u32x4*>(vb + (int64_t)(t * kPfKeys + 2 * p) * a.v_ss + 8 * c);
-      if (2 * p + 1 < nv) vc = *reinterpret_cast<const pf_u32x4*>(vb + (int64_t)(t * kPfKeys + 2 * p + 1) * a.v_ss + 8 * c);
+      sm_u32x4 va = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
+      if (2 * p < nv) va = *reinterpret_cast<const sm_u32x4*>(vb + (int64_t)(t * kSmKeys + 2 * p) * a.v_ss + 8 * c);
+      if (2 * p + 1 < nv) vc = *reinterpret_cast<const sm_u32x4*>(vb + (int64_t)(t * kSmKeys + 2 * p + 1) * a.v_ss + 8 * c);
       vreg[ii][0] = va; vreg[ii][1] = vc;
     }
   };
@@ -221,17 +193,17 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
   int t = next_tile(0);
   if (t < nt) load_tile(t);
   while (t < nt) {
-    const int n0 = t * kPfKeys, n1 = n0 + kPfKeys;
+    const int n0 = t * kSmKeys, n1 = n0 + kSmKeys;
     __syncthreads();
 #pragma unroll
     for (int ii = 0; ii < NK; ++ii) {
       const int u = tid + 256 * ii, key = u / CH, c = u % CH;
-      *reinterpret_cast<pf_u32x4*>(sK + key * KS + 8 * c) = kreg[ii];
+      *reinterpret_cast<sm_u32x4*>(sK + key * KS + 8 * c) = kreg[ii];
     }
 #pragma unroll
     for (int ii = 0; ii < NV; ++ii) {   // V transposed: 8 dwords [d][2p, 2p + 1] per chunk pair
       const int u = tid + 256 * ii, p = u & 31, c = u >> 5;
-      const pf_u32x4 va = vreg[ii][0], vc = vreg[ii][1];
+      const sm_u32x4 va = vreg[ii][0], vc = vreg[ii][1];
       uint32_t* dst = reinterpret_cast<uint32_t*>(sV + (8 * c) * VS + 2 * p);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -244,25 +216,13 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
     if (tn < nt) load_tile(tn);
 
     if (!skip || pf_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
-      // S^T = K Q^T for the two 32-key sub-blocks
-      pf_f32x16 s0, s1;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
-#pragma unroll
-      for (int s = 0; s < D / 16; ++s) {
-        const pf_u32x4 k0 = *reinterpret_cast<const pf_u32x4*>(sK + r * KS + 16 * s + 8 * h);
-        const pf_u32x4 k1 = *reinterpret_cast<const pf_u32x4*>(sK + (32 + r) * KS + 16 * s + 8 * h);
-        s0 = M::mma(k0, qf[s], s0);
-        s1 = M::mma(k1, qf[s], s1);
-      }
       float p[32];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { p[j] = s0[j] * a.scale_log2; p[16 + j] = s1[j] * a.scale_log2; }
+      T::scores(sK, qf, a.scale_log2, r, h, p);
       if (!skip || n1 > we.pmin) {   // some row of the wave does not see the whole tile through its prefix
         uint32_t ok = 0;
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
-          const int key = n0 + 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h;
+          const int key = n0 + sm_key_of(j, h);
           ok |= (uint32_t)(key < pre) << j;
         }
         if constexpr (MK == kPfFunc) {
@@ -272,7 +232,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
               if (valid) { lo = pf_clamp(frow[(int64_t)pp * a.f_sp], Lk); up = pf_clamp(frow[(int64_t)(pp + 1) * a.f_sp], Lk); }
 #pragma unroll
               for (int j = 0; j < 32; ++j) {
-                const int key = n0 + 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h;
+                const int key = n0 + sm_key_of(j, h);
                 ok |= (uint32_t)((lo <= key) & (key < up)) << j;
               }
             }
@@ -301,15 +261,15 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
       // O^T += V^T P^T
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {   // k-step: sub-block ks >> 1, step ks & 1: registers 8 ks .. 8 ks + 7 of p
-        pf_u32x4 pf;
+        sm_u32x4 pf;
 #pragma unroll
         for (int e = 0; e < 4; ++e) pf[e] = M::pack2(p[8 * ks + 2 * e], p[8 * ks + 2 * e + 1]);
 #pragma unroll
         for (int ii = 0; ii < D / 32; ++ii) {
           const uint16_t* vp = sV + (32 * ii + r) * VS + 16 * ks + 4 * h;
-          const pf_u32x2 lo = *reinterpret_cast<const pf_u32x2*>(vp);
-          const pf_u32x2 hi = *reinterpret_cast<const pf_u32x2*>(vp + 8);
-          const pf_u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
+          const sm_u32x2 lo = *reinterpret_cast<const sm_u32x2*>(vp);
+          const sm_u32x2 hi = *reinterpret_cast<const sm_u32x2*>(vp + 8);
+          const sm_u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
           o[ii] = M::mma(vf, pf, o[ii]);
         }
       }
@@ -326,20 +286,16 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
     for (int ii = 0; ii < D / 32; ++ii)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        pf_u32x2 x;
+        sm_u32x2 x;
         x[0] = M::pack2(o[ii][4 * g] * inv, o[ii][4 * g + 1] * inv);
         x[1] = M::pack2(o[ii][4 * g + 2] * inv, o[ii][4 * g + 3] * inv);
-        *reinterpret_cast<pf_u32x2*>(op + 32 * ii + 8 * g) = x;
+        *reinterpret_cast<sm_u32x2*>(op + 32 * ii + 8 * g) = x;
       }
     if (h == 0) {
       const int64_t li = a.cu_q ? (int64_t)hq * a.total_q + qrow0 + i : ((int64_t)b * a.Hq + hq) * a.Sq + i;
-      a.lse[li] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kPfLn2 : -INFINITY;   // v_log_f32 is log2
+      a.lse[li] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kSmLn2 : -INFINITY;   // v_log_f32 is log2
     }
   }
-}
-
-static inline bool pf_aligned(const void* p, int64_t s0, int64_t s1, int64_t s2) {
-  return ((uintptr_t)p % 16 == 0) && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
 }
 
 template <int DT, int D>
@@ -379,21 +335,21 @@ int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, in
     MI355_CHECK_ARG(func == nullptr, "prefill_attn: func is given but the mask kind is not 2 (a causal or plain call takes none)");
   }
   MI355_CHECK_ARG(skip_tiles == 0 || skip_tiles == 1, "prefill_attn: skip_tiles must be 0 or 1");
-  MI355_CHECK_ARG(B <= INT32_MAX && Hq <= INT32_MAX && Sq <= INT32_MAX - kPfRows && Sk <= INT32_MAX - kPfKeys &&
-                      total_q <= INT32_MAX - kPfRows && total_k <= INT32_MAX - kPfKeys,
+  MI355_CHECK_ARG(B <= INT32_MAX && Hq <= INT32_MAX && Sq <= INT32_MAX - kSmRows && Sk <= INT32_MAX - kSmKeys &&
+                      total_q <= INT32_MAX - kSmRows && total_k <= INT32_MAX - kSmKeys,
                   "prefill_attn: a dimension does not fit 31 bits");
   const int64_t rows = jagged ? total_q : B * Sq;
   if (B == 0 || rows == 0 || Sq == 0) return MI355_OK;
   MI355_CHECK_ARG(q && out && lse, "prefill_attn: null pointer");
-  MI355_CHECK_ARG(pf_aligned(q, q_stride_b, q_stride_s, q_stride_h) && (uintptr_t)out % 16 == 0,
+  MI355_CHECK_ARG(sm_aligned(q, q_stride_b, q_stride_s, q_stride_h) && (uintptr_t)out % 16 == 0,
                   "prefill_attn: q and out need 16-byte aligned rows (base aligned, strides multiples of 8 elements)");
   if (jagged ? total_k > 0 : Sk > 0) {
     MI355_CHECK_ARG(k && v, "prefill_attn: null k / v pointer");
-    MI355_CHECK_ARG(pf_aligned(k, k_stride_b, k_stride_s, k_stride_h) && pf_aligned(v, v_stride_b, v_stride_s, v_stride_h),
+    MI355_CHECK_ARG(sm_aligned(k, k_stride_b, k_stride_s, k_stride_h) && sm_aligned(v, v_stride_b, v_stride_s, v_stride_h),
                     "prefill_attn: k / v rows need 16-byte alignment (base aligned, strides multiples of 8 elements)");
   }
   if (mask == kPfFunc) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "prefill_attn: func is null or misaligned");
-  const int64_t nqt = ceil_div(Sq, (int64_t)kPfRows);   // jagged: Sq is max_seqlen_q
+  const int64_t nqt = ceil_div(Sq, (int64_t)kSmRows);   // jagged: Sq is max_seqlen_q
   const int64_t nblocks = nqt * B * Hq;
   MI355_CHECK_ARG(nblocks <= INT32_MAX, "prefill_attn: launch too large");
 
@@ -407,7 +363,7 @@ int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, in
   c.total_q = total_q; c.total_k = total_k;
   c.B = (int)B; c.Sq = (int)Sq; c.Sk = (int)Sk; c.Hq = (int)Hq; c.G = (int)(Hq / Hkv); c.nqt = (int)nqt;
   c.n_func = (int)n_func; c.skip = skip_tiles;
-  c.scale_log2 = softmax_scale * kPfLog2e;
+  c.scale_log2 = softmax_scale * kSmLog2e;
   const dim3 grid((unsigned)nblocks);
   if (dtype == kBF16) {
     if (D == 64) pf_launch<kBF16, 64>(mask, grid, stream, c);

@@ -365,6 +365,16 @@ def ptr(t: Optional[torch.Tensor]):
     return c_p(t.data_ptr())
 
 
+def rows_aligned(t: torch.Tensor) -> torch.Tensor:
+    """For kernels that read rows in 16-byte pieces of 2-byte elements: a view whose strides or base are not multiples of 8
+    elements is copied (the unbind(2) views of a packed [B, S, 3, H, D] buffer are not)."""
+    if t.numel() == 0:
+        return t
+    if t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]):
+        return t
+    return t.contiguous()
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _cur_device = getattr(torch._C, "_cuda_getDevice", None)
 

@@ -21,9 +21,10 @@ from typing import Optional
 import torch
 
 import mi355_native as N
+from mi355_native import rows_aligned as _rows_aligned
 
-KEY_TILE = 64      # keys per tile (csrc/prefill_attn.hip: kPfKeys)
-ROW_TILE = 128     # query rows per workgroup (kPfRows)
+KEY_TILE = 64      # keys per tile (csrc/softmax_tile_dev.h: kSmKeys)
+ROW_TILE = 128     # query rows per workgroup (kSmRows)
 MASK_NONE, MASK_CAUSAL, MASK_FUNC = 0, 1, 2
 
 
@@ -81,16 +82,6 @@ def _require_gpu(**tensors):
     for name, t in tensors.items():
         if t is not None and not t.is_cuda:
             raise PrefillAttnError(f"{name} must be a GPU tensor (there is no CPU path), got device {t.device}")
-
-
-def _rows_aligned(t: torch.Tensor) -> torch.Tensor:
-    """The kernel reads rows in 16-byte pieces: a view whose strides or base are not multiples of 8 elements is copied
-    (the unbind(2) views of a packed [B, S, 3, H, D] buffer are not)."""
-    if t.numel() == 0:
-        return t
-    if t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]):
-        return t
-    return t.contiguous()
 
 
 def _forward(q, k, v, cu_q, cu_k, max_q, mask, func, scale, skip_tiles):

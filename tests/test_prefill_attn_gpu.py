@@ -64,7 +64,7 @@ def test_against_the_twin(case):
     if case.form == "strided":   # still three views of one packed buffer: nothing was copied on the way to the kernel
         assert not g["q"].is_contiguous() and not g["k"].is_contiguous() and not g["v"].is_contiguous()
         assert g["q"]._base is g["k"]._base is g["v"]._base and g["q"]._base is not None
-        from prefill_attn import _rows_aligned
+        from mi355_native import rows_aligned as _rows_aligned
         assert all(_rows_aligned(g[n]) is g[n] for n in ("q", "k", "v"))
     out, lse = _run(g)
     Hq = case.Hq
