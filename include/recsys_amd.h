@@ -1430,6 +1430,31 @@ int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, in
                        int64_t func_stride_h, int64_t func_stride_f, int64_t func_stride_s, float softmax_scale,
                        int skip_tiles, void* out, float* lse, int dtype, hipStream_t stream);
 
+/* ---- softmax attention backward: dq, dk, dv of mi355_prefill_attn (csrc/softmax_attn_bwd.hip) ----
+ * The training side of the same three flash-attention calls (examples/sid_gr/model/jagged_flash_attn_block.py runs them under
+ * autograd).  The arguments up to skip_tiles are those of mi355_prefill_attn with the same meaning (forms, strides, masks,
+ * clamped cu_seqlens); in the jagged form Sk carries max_seqlen_k, which bounds the dK / dV launch the way Sq = max_seqlen_q
+ * bounds the forward's: both must be at least the longest sequence.
+ *   out   the forward's output, contiguous ([B, Sq, Hq, D] / [total_q, Hq, D]);
+ *   dout  its gradient, same shape, at the given batch / row / head strides (batch ignored in the jagged form), rows 16-byte aligned;
+ *   lse   the forward's, fp32 natural log ([B, Hq, Sq] / [Hq, total_q]);
+ *   delta workspace, fp32, the shape of lse: written (delta_i = sum_d dout_id out_id) by the first launch, read by the second;
+ *   dq [B, Sq, Hq, D] / [total_q, Hq, D], dk and dv [B, Sk, Hkv, D] / [total_k, Hkv, D]: contiguous, in `dtype`.
+ * P is recomputed from lse, dS = P (dP - delta); P and dS are rounded once to `dtype` for the products, sums are fp32, each
+ * gradient is rounded once.  dk / dv of a kv head sum over its Hq / Hkv query heads in head order inside one workgroup.
+ * Every element of dq / dk / dv that belongs to a sequence is written (the caller zeroes nothing): a row with lse = -inf gets
+ * dq = 0 and a key no query sees dk = dv = 0 exactly.  n_func is at most 129.  skip_tiles = 0 gives bitwise the same result.
+ * Two launches, no atomics, no allocation, no host read: capturable and bitwise reproducible. */
+int mi355_softmax_attn_bwd(const void* q, int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, const void* k,
+                           int64_t k_stride_b, int64_t k_stride_s, int64_t k_stride_h, const void* v, int64_t v_stride_b,
+                           int64_t v_stride_s, int64_t v_stride_h, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                           int64_t B, int64_t Sq, int64_t Sk, int64_t total_q, int64_t total_k, int64_t Hq, int64_t Hkv, int64_t D,
+                           int mask, const int32_t* func, int64_t n_func, int64_t func_heads, int64_t func_stride_b,
+                           int64_t func_stride_h, int64_t func_stride_f, int64_t func_stride_s, float softmax_scale,
+                           int skip_tiles, const void* out, const void* dout, int64_t dout_stride_b, int64_t dout_stride_s,
+                           int64_t dout_stride_h, const float* lse, float* delta, void* dq, void* dk, void* dv, int dtype,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """`flash_attn.cute.interface.flash_attn_func` as the reference calls it: returns (out, lse).  arbitrary=True takes
-aux_tensors=[arbitrary_func]; the linear_*_block_sparse_tensors are accepted and not read."""
-import prefill_attn as _P
+aux_tensors=[arbitrary_func]; the linear_*_block_sparse_tensors (forward and backward ones) are accepted and not read.
+Differentiable in q, k, v (softmax_attn.py); lse carries no gradient."""
+import softmax_attn as _P
 
 
 def flash_attn_func(q, k, v, softmax_scale=None, causal=False, arbitrary=False, linear_k_block_sparse_tensors=None,

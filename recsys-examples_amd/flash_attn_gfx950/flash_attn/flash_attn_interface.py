@@ -1,7 +1,7 @@
 """`flash_attn.flash_attn_interface` of flash-attn 2 as far as the reference calls it: both functions return `out` alone.
 Arguments this kernel does not carry (dropout, window, softcap, alibi, attention probabilities) are refused unless they have
-their defaults."""
-import prefill_attn as _P
+their defaults.  Both are differentiable in q, k, v (softmax_attn.py)."""
+import softmax_attn as _P
 
 
 def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,

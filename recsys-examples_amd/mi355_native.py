@@ -256,6 +256,11 @@ _SIGS = {
                            c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # cu_q, cu_k, B, Sq, Sk, totals, Hq, Hkv, D
                            c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # mask, func, n_func, heads, strides
                            c_f, c_int, c_p, c_p, c_int, c_p],  # scale, skip_tiles, out, lse, dtype, stream
+    "mi355_softmax_attn_bwd": [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64,  # q, k, v + strides
+                               c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # cu_q, cu_k, B, Sq, Sk, totals, Hq, Hkv, D
+                               c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,  # mask, func, n_func, heads, strides
+                               c_f, c_int, c_p, c_p, c_i64, c_i64, c_i64,  # scale, skip_tiles, out, dout + strides
+                               c_p, c_p, c_p, c_p, c_p, c_int, c_p],  # lse, delta, dq, dk, dv, dtype, stream
     "mi355_abi_version": [],
     "mi355_last_error": [],
 }
