@@ -10,11 +10,12 @@
 //   xh = (x - mean) * rstd;  gn = fmaf(xh, w_h, b_h);  t = gn * u;  y = drop(t), or [drop0(u) | drop1(x) | drop2(t)]
 //   backward: dt = drop2'(dy_t);  du = fmaf(dt, gn, drop0'(dy_u));  gp = dt * u;  g = w_h * gp;  c1 = sum(xh * g) / L;
 //   c2 = sum(g) / L;  dx = (g - (xh * c1 + c2)) * rstd + drop1'(dy_x);  dw_h = sum of gp * xh;  db_h = sum of gp
-// The dropout is that of norm_ops.hip (norm_dev.h) with col the column in the whole row.
+// The dropout is that of norm_ops.hip (norm_dev.h) with col the column in the whole row.  Decomposition, the forward's stores, the
+// ladder, the grid rule and the dw / db launch are those of norm_dev.h.
 //
 // Two layouts.
 //   Fast: a head is a whole number of 16-byte pieces, their count PPH = L / V a power of two <= 64, every base pointer and
-//   stride a multiple of 16 bytes.  The decomposition is that of norm_ops.hip (piece i of the row belongs to thread i mod T; a
+//   stride a multiple of 16 bytes.  The decomposition is that of norm_dev.h (piece i of the row belongs to thread i mod T; a
 //   wave owns a row for D <= 2048, a workgroup above), so a head is PPH neighbouring lanes of one round and never leaves its
 //   wave: the per-head sums are butterflies over lane groups (DPP quad_perm / row_half_mirror / row_mirror for 2 .. 16 lanes,
 //   ds_bpermute for 32 and 64), every lane of a group ends with the same bits, nothing goes through LDS.  The backward keeps
@@ -30,7 +31,7 @@
 
 namespace mi355 {
 
-struct GnArgs {
+struct GnArgs : NormDropout {
   uintptr_t x, u, y, w, b, dy, dx, du;                // y 0: not written
   int64_t x_stride, u_s0, u_s1, y_stride, dy_stride, dx_stride, du_s0, du_s1;   // bytes
   float* mean;
@@ -41,9 +42,8 @@ struct GnArgs {
   int D, H, L;
   int lg;              // fast: log2 of the pieces of a head; general: log2 of the lanes of a (row, head)
   int slots;           // general backward: lane groups = slots * H
-  float eps, den;      // den = 1 - p
-  uint32_t thr, seed_lo, seed_hi;
-  int w_f32, drop, concat;
+  float eps;
+  int w_f32, concat;
 };
 
 #define GN_DPP(v, ctrl) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false))
@@ -64,40 +64,48 @@ __device__ __forceinline__ float ld_param1(uintptr_t p, int i, int f32, int dt) 
   return dt == kBF16 ? bf16_to_f32(h) : f16_to_f32(h);
 }
 
-// The forward's stores of one piece (also the backward's compute_y)
-template <int DT, int V>
-__device__ __forceinline__ void gn_store_y(const GnArgs& a, int64_t row, int c, const float (&x)[V], const float (&u)[V], float w,
-                                           float b, float mean, float rstd) {
-  constexpr uintptr_t EB = Vec<DT, V>::EB;
-  const uintptr_t yr = a.y + (uintptr_t)row * a.y_stride + (uintptr_t)c * EB;
-  float t[V];
-#pragma unroll
-  for (int e = 0; e < V; ++e) t[e] = __fmul_rn(norm_ln(norm_xh(x[e], mean, rstd), w, b), u[e]);
-  if (a.concat) {
-    float p0[V], p1[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) { p0[e] = u[e]; p1[e] = x[e]; }
-    if (a.drop) {
-      drop_apply<V>(a, row, c, 0u, p0);
-      drop_apply<V>(a, row, c, 1u, p1);
-      drop_apply<V>(a, row, c, 2u, t);
-    }
-    Vec<DT, V>::st(yr, p0);
-    Vec<DT, V>::st(yr + (uintptr_t)a.D * EB, p1);
-    Vec<DT, V>::st(yr + (uintptr_t)a.D * 2 * EB, t);
-    return;
-  }
-  if (a.drop) drop_apply<V>(a, row, c, 0u, t);
-  Vec<DT, V>::st(yr, t);
-}
-
-// The backward of one piece up to the sums: y again, the masks, du stored; g: dy_t in, gp = dt u out; ex: dy_x in, dropped out
-template <int DT, int V>
-__device__ __forceinline__ void gn_bwd_head(const GnArgs& a, int64_t row, int c, uint32_t duo, const float (&x)[V], float (&g)[V],
-                                            const float (&u)[V], float (&ex)[V], float w, float b, float mean, float rstd) {
+// The backward of one piece up to the sums: y again, the masks, du stored (at byte offset duo of the row); g: dy_t in,
+// gp = dt u out; ex: dy_x in, dropped out.  Two statement orders, chosen per instantiation by measurement; the values are the same.
+// gn_bwd_head: the masks of dt and dy_x before the du load, the order of the LN-mul-dropout backward (norm_dev.h).  Every fast
+// kernel but one and the general layout's apply kernel use it.  At CAP 32 wave rows (D = 2048) it takes 165 us where the order
+// below takes 585 (16 384 x (8, 256) bf16): the order decides how hipcc stages that kernel's AGPR copies.
+// gn_bwd_head_cap16: the du load before the masks, the order this file had from the start.  hstu_gn_bwd_kernel<DT, V, 16, false>
+// (wave rows, D in 513 .. 1024) alone keeps it: with the order above that kernel took 54.4 us against 52.1 at 16 384 x (8, 128)
+// bf16 and 106.5 against 102.9 at 32 768.
+template <int DT, int V, class A, class W>
+__device__ __forceinline__ void gn_bwd_head(const A& a, int64_t row, int c, uint32_t duo, const float (&x)[V], float (&g)[V],
+                                             const float (&u)[V], float (&ex)[V], const W& w, const W& b, float mean, float rstd) {
   constexpr uintptr_t EB = Vec<DT, V>::EB;
   const bool cat = a.concat != 0;
-  if (a.y) gn_store_y<DT, V>(a, row, c, x, u, w, b, mean, rstd);
+  if (a.y) mul_store_y<DT, V>(a, row, c, x, u, w, b, mean, rstd);
+  if (a.drop) {
+    drop_apply<V>(a, row, c, cat ? 2u : 0u, g);   // dt
+    if (cat) drop_apply<V>(a, row, c, 1u, ex);
+  }
+  float duv[V];
+  if (cat) {
+    Vec<DT, V>::ld(a.dy + (uintptr_t)row * a.dy_stride + (uintptr_t)c * EB, duv);
+    if (a.drop) drop_apply<V>(a, row, c, 0u, duv);
+  } else {
+#pragma unroll
+    for (int e = 0; e < V; ++e) duv[e] = 0.f;
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    const float ln = norm_ln(norm_xh(x[e], mean, rstd), norm_par(w, e), norm_par(b, e));
+    duv[e] = __fmaf_rn(g[e], ln, duv[e]);
+    g[e] *= u[e];
+  }
+  Vec<DT, V>::st(a.du + (uintptr_t)row * a.du_s0 + duo, duv);
+}
+
+template <int DT, int V>
+__device__ __forceinline__ void gn_bwd_head_cap16(const GnArgs& a, int64_t row, int c, uint32_t duo, const float (&x)[V],
+                                                  float (&g)[V], const float (&u)[V], float (&ex)[V], float w, float b, float mean,
+                                                  float rstd) {
+  constexpr uintptr_t EB = Vec<DT, V>::EB;
+  const bool cat = a.concat != 0;
+  if (a.y) mul_store_y<DT, V>(a, row, c, x, u, w, b, mean, rstd);
   float duv[V];
   if (cat) Vec<DT, V>::ld(a.dy + (uintptr_t)row * a.dy_stride + (uintptr_t)c * EB, duv);
   else {
@@ -120,14 +128,12 @@ __device__ __forceinline__ void gn_bwd_head(const GnArgs& a, int64_t row, int c,
   Vec<DT, V>::st(a.du + (uintptr_t)row * a.du_s0 + duo, duv);
 }
 
-// ---- the fast layout ----
+// ---- the fast layout: RowPieces and mul_store_y of norm_dev.h; the statistics are per head ----
 template <int DT, int V, int CAP, bool BLOCK>
 __global__ __launch_bounds__(256) void hstu_gn_fwd_kernel(const GnArgs a) {
-  constexpr int NP = CAP / V, T = BLOCK ? 256 : 64;
+  constexpr int NP = CAP / V;
   constexpr uintptr_t EB = Vec<DT, V>::EB;
-  const int tid = BLOCK ? (int)threadIdx.x : lane_id();
-  const int64_t row0 = BLOCK ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t step = BLOCK ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
+  const RowPieces<V, CAP, BLOCK> p;
   const float fL = (float)a.L;
   const int lg = a.lg;
   float w[NP], b[NP];
@@ -135,22 +141,22 @@ __global__ __launch_bounds__(256) void hstu_gn_fwd_kernel(const GnArgs a) {
   int hd[NP];
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
-    const int c = (tid + k * T) * V;
+    const int c = p.col(k);
     w[k] = 1.f; b[k] = 0.f; uo[k] = 0; hd[k] = 0;
     if (c < a.D) {
-      const int h = (tid + k * T) >> lg;
+      const int h = p.piece(k) >> lg;
       hd[k] = h;
       w[k] = ld_param1(a.w, h, a.w_f32, DT);
       b[k] = ld_param1(a.b, h, a.w_f32, DT);
       uo[k] = (uint32_t)((int64_t)h * a.u_s1 + (int64_t)(c - h * a.L) * (int64_t)EB);
     }
   }
-  for (int64_t row = row0; row < a.N; row += step) {
+  for (int64_t row = p.row0; row < a.N; row += p.step) {
     float x[NP][V], u[NP][V];
     const uintptr_t xr = a.x + (uintptr_t)row * a.x_stride, ur = a.u + (uintptr_t)row * a.u_s0;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      const int c = (tid + k * T) * V;
+      const int c = p.col(k);
 #pragma unroll
       for (int e = 0; e < V; ++e) { x[k][e] = 0.f; u[k][e] = 0.f; }
       if (c < a.D) {
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void hstu_gn_fwd_kernel(const GnArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      const int c = (tid + k * T) * V;
+      const int c = p.col(k);
       float s = 0.f, q = 0.f;
 #pragma unroll
       for (int e = 0; e < V; ++e) s += x[k][e];
@@ -172,11 +178,11 @@ __global__ __launch_bounds__(256) void hstu_gn_fwd_kernel(const GnArgs a) {
       }
       const float rstd = 1.f / sqrtf(seg_sum(q, lg) / fL + a.eps);
       if (c < a.D) {
-        if (((tid + k * T) & ((1 << lg) - 1)) == 0) {
+        if ((p.piece(k) & ((1 << lg) - 1)) == 0) {
           a.mean[row * a.H + hd[k]] = mean;
           a.rstd[row * a.H + hd[k]] = rstd;
         }
-        gn_store_y<DT, V>(a, row, c, x[k], u[k], w[k], b[k], mean, rstd);
+        mul_store_y<DT, V>(a, row, c, x[k], u[k], w[k], b[k], mean, rstd);
       }
     }
   }
@@ -184,14 +190,11 @@ __global__ __launch_bounds__(256) void hstu_gn_fwd_kernel(const GnArgs a) {
 
 template <int DT, int V, int CAP, bool BLOCK>
 __global__ __launch_bounds__(256) void hstu_gn_bwd_kernel(const GnArgs a) {
-  constexpr int NP = CAP / V, T = BLOCK ? 256 : 64;
+  constexpr int NP = CAP / V;
   constexpr uintptr_t EB = Vec<DT, V>::EB;
   constexpr int kFoldH = kNormWaveMaxD / 4;   // heads of a wave row at most: fp32 pieces of 4, one piece a head
   __shared__ float s_fold[BLOCK ? 1 : 4 * 2 * kFoldH];
-  const int tid = BLOCK ? (int)threadIdx.x : lane_id();
-  const int wv = threadIdx.x >> 6;
-  const int64_t row0 = BLOCK ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wv;
-  const int64_t step = BLOCK ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
+  const RowPieces<V, CAP, BLOCK> p;
   const float fL = (float)a.L;
   const int lg = a.lg;
   const bool cat = a.concat != 0;
@@ -200,10 +203,10 @@ __global__ __launch_bounds__(256) void hstu_gn_bwd_kernel(const GnArgs a) {
   int hd[NP];
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
-    const int c = (tid + k * T) * V;
+    const int c = p.col(k);
     w[k] = 1.f; b[k] = 0.f; dwp[k] = 0.f; dbp[k] = 0.f; uo[k] = duo[k] = 0; hd[k] = 0;
     if (c < a.D) {
-      const int h = (tid + k * T) >> lg;
+      const int h = p.piece(k) >> lg;
       hd[k] = h;
       w[k] = ld_param1(a.w, h, a.w_f32, DT);
       b[k] = ld_param1(a.b, h, a.w_f32, DT);
@@ -211,13 +214,13 @@ __global__ __launch_bounds__(256) void hstu_gn_bwd_kernel(const GnArgs a) {
       duo[k] = (uint32_t)((int64_t)h * a.du_s1 + (int64_t)(c - h * a.L) * (int64_t)EB);
     }
   }
-  for (int64_t row = row0; row < a.N; row += step) {
+  for (int64_t row = p.row0; row < a.N; row += p.step) {
     float x[NP][V], g[NP][V], u[NP][V], ex[NP][V];
     const uintptr_t xr = a.x + (uintptr_t)row * a.x_stride, ur = a.u + (uintptr_t)row * a.u_s0;
     const uintptr_t dyr = a.dy + (uintptr_t)row * a.dy_stride;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      const int c = (tid + k * T) * V;
+      const int c = p.col(k);
 #pragma unroll
       for (int e = 0; e < V; ++e) { x[k][e] = 0.f; g[k][e] = 0.f; u[k][e] = 0.f; ex[k][e] = 0.f; }
       if (c < a.D) {
@@ -229,13 +232,14 @@ __global__ __launch_bounds__(256) void hstu_gn_bwd_kernel(const GnArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      const int c = (tid + k * T) * V;
+      const int c = p.col(k);
       const bool live = c < a.D;
       float mean = 0.f, rstd = 0.f, s0 = 0.f, s1 = 0.f;   // sum(xh g), sum(g) of this thread's piece
       if (live) {
         mean = a.mean[row * a.H + hd[k]];
         rstd = a.rstd[row * a.H + hd[k]];
-        gn_bwd_head<DT, V>(a, row, c, duo[k], x[k], g[k], u[k], ex[k], w[k], b[k], mean, rstd);
+        if constexpr (CAP == 16 && !BLOCK) gn_bwd_head_cap16<DT, V>(a, row, c, duo[k], x[k], g[k], u[k], ex[k], w[k], b[k], mean, rstd);
+        else gn_bwd_head<DT, V>(a, row, c, duo[k], x[k], g[k], u[k], ex[k], w[k], b[k], mean, rstd);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           const float xh = norm_xh(x[k][e], mean, rstd), gp = g[k][e];
@@ -265,13 +269,13 @@ __global__ __launch_bounds__(256) void hstu_gn_bwd_kernel(const GnArgs a) {
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
     const float sw = seg_sum(dwp[k], lg), sb = seg_sum(dbp[k], lg);
-    if ((tid + k * T) * V < a.D && ((tid + k * T) & ((1 << lg) - 1)) == 0) {
+    if (p.col(k) < a.D && (p.piece(k) & ((1 << lg) - 1)) == 0) {
       if constexpr (BLOCK) {
         pw[hd[k]] = sw;
         pb[hd[k]] = sb;
       } else {
-        s_fold[(wv * 2) * kFoldH + hd[k]] = sw;
-        s_fold[(wv * 2 + 1) * kFoldH + hd[k]] = sb;
+        s_fold[(p.wv * 2) * kFoldH + hd[k]] = sw;
+        s_fold[(p.wv * 2 + 1) * kFoldH + hd[k]] = sb;
       }
     }
   }
@@ -381,7 +385,7 @@ __global__ __launch_bounds__(256) void hstu_gn_apply_kernel(const GnArgs a) {
     Vec<DT, V>::ld(a.x + (uintptr_t)row * a.x_stride + (uintptr_t)c * EB, x);
     Vec<DT, V>::ld(a.u + (uintptr_t)row * a.u_s0 + (uintptr_t)h * a.u_s1 + (uintptr_t)(c - h * a.L) * EB, u);
     if constexpr (!BWD) {
-      gn_store_y<DT, V>(a, row, c, x, u, w, b, mean, rstd);
+      mul_store_y<DT, V>(a, row, c, x, u, w, b, mean, rstd);
     } else {
       const uintptr_t dyr = a.dy + (uintptr_t)row * a.dy_stride;
       float g[V], ex[V];
@@ -406,14 +410,6 @@ __global__ __launch_bounds__(256) void hstu_gn_apply_kernel(const GnArgs a) {
 }
 
 // ---- host ----
-static inline int gn_fast_fwd_blocks(int64_t rows, int64_t D) {
-  const int64_t g = D <= kNormWaveMaxD ? ceil_div(rows, 4) : rows;
-  return (int)(g < 1 ? 1 : g > 2048 ? 2048 : g);
-}
-static inline int gn_fast_bwd_blocks(int64_t rows, int64_t D) {
-  const int64_t g = D <= kNormWaveMaxD ? ceil_div(rows, 4) : rows, cap = D <= kNormWaveMaxD ? 512 : 1024;
-  return (int)(g < 1 ? 1 : g > cap ? cap : g);
-}
 // general layout: log2 of the lanes of a (row, head): the largest power of two <= L / 4, in 1 .. 64
 static inline int gn_gen_lg(int64_t L) {
   int lg = 0;
@@ -435,24 +431,14 @@ static inline int gn_apply_blocks(int64_t pieces) {
 
 using namespace mi355;
 
-template <int DT, int V, int CAP, bool BLOCK, bool BWD>
-static void gn_go(int grid, const GnArgs& a, hipStream_t stream) {
-  if constexpr (BWD) hstu_gn_bwd_kernel<DT, V, CAP, BLOCK><<<dim3(grid), dim3(256), 0, stream>>>(a);
-  else hstu_gn_fwd_kernel<DT, V, CAP, BLOCK><<<dim3(grid), dim3(256), 0, stream>>>(a);
-}
-template <int DT, int V, bool BWD>
-static void gn_fast_cap(int grid, const GnArgs& a, hipStream_t stream) {
-  if (a.D <= 512) gn_go<DT, V, 8, false, BWD>(grid, a, stream);
-  else if (a.D <= 1024) gn_go<DT, V, 16, false, BWD>(grid, a, stream);
-  else if (a.D <= kNormWaveMaxD) gn_go<DT, V, 32, false, BWD>(grid, a, stream);
-  else if (a.D <= 4096) gn_go<DT, V, 16, true, BWD>(grid, a, stream);
-  else gn_go<DT, V, 32, true, BWD>(grid, a, stream);
-}
+// the fast kernels through the ladder of norm_dev.h, without its V = 1 arm: the fast layout is made of 16-byte pieces
 template <bool BWD>
 static void gn_fast(int dtype, int grid, const GnArgs& a, hipStream_t stream) {
-  if (dtype == kF32) gn_fast_cap<kF32, 4, BWD>(grid, a, stream);
-  else if (dtype == kBF16) gn_fast_cap<kBF16, 8, BWD>(grid, a, stream);
-  else gn_fast_cap<kF16, 8, BWD>(grid, a, stream);
+  norm_dispatch<false>(dtype, 0, a.D, [&](auto s) {
+    using S = decltype(s);
+    if constexpr (BWD) hstu_gn_bwd_kernel<S::DT, S::V, S::CAP, S::BLOCK><<<dim3(grid), dim3(256), 0, stream>>>(a);
+    else hstu_gn_fwd_kernel<S::DT, S::V, S::CAP, S::BLOCK><<<dim3(grid), dim3(256), 0, stream>>>(a);
+  });
 }
 template <int DT, int V, bool BWD>
 static void gn_general_dt(int v, int stats_grid, const GnArgs& a, hipStream_t stream) {
@@ -478,21 +464,10 @@ static int gn_fast_lg(int64_t L, int v) {
   return lg;
 }
 
-#define GN_CHECK_COMMON(NAME, rows, H, L, D, dtype, wdtype, p)                                                      \
-  MI355_CHECK_ARG(D > 0 && D <= kNormMaxD, NAME ": D must be in 1 .. 8192");                                        \
-  MI355_CHECK_ARG(norm_ebytes(dtype) != 0, NAME ": unsupported dtype");                                             \
-  MI355_CHECK_ARG(wdtype == kF32 || wdtype == dtype, NAME ": weight and bias are fp32 or have the dtype of the rows"); \
-  MI355_CHECK_ARG(rows >= 0 && rows < ((int64_t)1 << 31), NAME ": rows must be in 0 .. 2^31");                      \
-  MI355_CHECK_ARG(H >= 1 && L >= 1 && H * L == D, NAME ": the heads must fill the row, H * L == D");                \
+#define GN_CHECK_COMMON(NAME, rows, H, L, D, dtype, wdtype, p)                                       \
+  NORM_CHECK_COMMON(NAME, rows, D, dtype, wdtype, "weight and bias are");                            \
+  MI355_CHECK_ARG(H >= 1 && L >= 1 && H * L == D, NAME ": the heads must fill the row, H * L == D"); \
   MI355_CHECK_ARG(p >= 0.0 && p < 1.0, NAME ": dropout_ratio must be in [0, 1)")
-
-static void gn_set_dropout(GnArgs& a, double p, int training, uint64_t seed) {
-  a.thr = (uint32_t)(uint64_t)(p * 4294967296.0);   // floor(p 2^32), p in [0, 1)
-  a.den = 1.0f - (float)p;
-  a.drop = training != 0 && a.thr > 0;
-  a.seed_lo = (uint32_t)seed;
-  a.seed_hi = (uint32_t)(seed >> 32);
-}
 
 extern "C" int mi355_hstu_gn_mul_dropout_fwd(const void* x, int64_t x_stride, const void* u, int64_t u_stride0, int64_t u_stride1,
                                              int64_t H, int64_t L, int64_t rows, int64_t D, int dtype, const void* weight,
@@ -516,11 +491,11 @@ extern "C" int mi355_hstu_gn_mul_dropout_fwd(const void* x, int64_t x_stride, co
   a.x_stride = x_stride * eb; a.u_s0 = u_stride0 * eb; a.u_s1 = u_stride1 * eb; a.y_stride = y_stride * eb;
   a.mean = mean; a.rstd = rstd; a.N = rows; a.D = (int)D; a.H = (int)H; a.L = (int)L; a.eps = eps;
   a.w_f32 = weight_dtype == kF32; a.concat = concat_ux != 0;
-  gn_set_dropout(a, dropout_ratio, training, seed);
+  norm_set_dropout(a, dropout_ratio, training, seed);
   const int flg = nv.v != 1 ? gn_fast_lg(L, nv.v) : -1;
   if (flg >= 0) {
     a.lg = flg;
-    gn_fast<false>(dtype, gn_fast_fwd_blocks(rows, D), a, stream);
+    gn_fast<false>(dtype, norm_row_blocks(rows, D, false), a, stream);
   } else {
     a.lg = gn_gen_lg(L);
     const int64_t blocks = ceil_div((rows * H) << a.lg, 256);
@@ -533,7 +508,7 @@ extern "C" int mi355_hstu_gn_mul_dropout_fwd(const void* x, int64_t x_stride, co
 // the partials of either layout and the general layout's (c1, c2) of every (row, head)
 extern "C" int64_t mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(int64_t rows, int64_t H, int64_t L) {
   if (rows < 0 || H < 1 || L < 1 || H * L > kNormMaxD) return 0;
-  const int64_t fast = (int64_t)gn_fast_bwd_blocks(rows, H * L) * H, gen = (int64_t)gn_gen_slots(rows, H, L) * H;
+  const int64_t fast = (int64_t)norm_row_blocks(rows, H * L, true) * H, gen = (int64_t)gn_gen_slots(rows, H, L) * H;
   return ((fast > gen ? fast : gen) * 2 + rows * H * 2) * 4;
 }
 
@@ -573,13 +548,13 @@ extern "C" int mi355_hstu_gn_mul_dropout_bwd(const void* dy, int64_t dy_stride, 
   a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.partial = (float*)workspace;
   a.N = rows; a.D = (int)D; a.H = (int)H; a.L = (int)L;
   a.w_f32 = weight_dtype == kF32; a.concat = concat_ux != 0;
-  gn_set_dropout(a, dropout_ratio, training, seed);
+  norm_set_dropout(a, dropout_ratio, training, seed);
   int partial_rows = 0;
   if (rows > 0) {
     const int flg = nv.v != 1 ? gn_fast_lg(L, nv.v) : -1;
     if (flg >= 0) {
       a.lg = flg;
-      partial_rows = gn_fast_bwd_blocks(rows, D);
+      partial_rows = norm_row_blocks(rows, D, true);
       gn_fast<true>(dtype, partial_rows, a, stream);
     } else {
       a.lg = gn_gen_lg(L);
@@ -589,10 +564,5 @@ extern "C" int mi355_hstu_gn_mul_dropout_bwd(const void* dy, int64_t dy_stride, 
     }
     MI355_LAUNCH_CHECK();
   }
-  const dim3 grid((unsigned)ceil_div(H, 64), 2);
-  if (weight_dtype == kF32) hstu_norm_dwdb_kernel<kF32><<<grid, dim3(1024), 0, stream>>>(a.partial, partial_rows, (int)H, dweight, dbias);
-  else if (weight_dtype == kBF16) hstu_norm_dwdb_kernel<kBF16><<<grid, dim3(1024), 0, stream>>>(a.partial, partial_rows, (int)H, dweight, dbias);
-  else hstu_norm_dwdb_kernel<kF16><<<grid, dim3(1024), 0, stream>>>(a.partial, partial_rows, (int)H, dweight, dbias);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return norm_launch_dwdb(a.partial, partial_rows, (int)H, weight_dtype, dweight, dbias, stream);
 }

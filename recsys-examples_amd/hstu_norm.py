@@ -95,6 +95,28 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _du_layout(du: Optional[torch.Tensor], u: torch.Tensor, D: int):
+    """(du, stride0, stride1): a new tensor like u, or the caller's after the check against u"""
+    if du is None:
+        du = torch.empty_like(u)
+    if du.shape != u.shape or (du.stride(-1) != 1 and du.size(-1) != 1):
+        raise ValueError("du must have the shape of u and a contiguous last dimension")
+    _, ds0, ds1, _, _ = _u_layout(du, D, "du")
+    return du, ds0, ds1
+
+
+def _new_y(x: torch.Tensor, width: int) -> torch.Tensor:
+    return torch.empty((x.size(0), width), dtype=x.dtype, device=x.device)
+
+
+def _new_stat(x: torch.Tensor, n: int) -> torch.Tensor:
+    return torch.empty((n,), dtype=torch.float32, device=x.device)
+
+
+def _new_dparam(x: torch.Tensor, weight: torch.Tensor, n: int) -> torch.Tensor:
+    return torch.empty((n,), dtype=weight.dtype, device=x.device)
+
+
 def triton_weighted_layer_norm_fwd(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
                                    mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None
                                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int, int]:
@@ -109,12 +131,12 @@ def triton_weighted_layer_norm_fwd(x: torch.Tensor, weight: Optional[torch.Tenso
         assert bias is not None
         _check_params(weight, bias, D)
         weight, bias = weight.contiguous(), bias.contiguous()
-    y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    y = _new_y(x, D)
     given = mean is not None and rstd is not None
     if mean is None:
-        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        mean = _new_stat(x, rows)
     if rstd is None:
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        rstd = _new_stat(x, rows)
     block_d, num_warps = _launch_params(D, x.element_size())
     N.check(N.lib().mi355_hstu_layer_norm_fwd(
         N.ptr(x), _stride(x), rows, D, N.dt(x), N.ptr(weight), N.ptr(bias), N.dt(weight) if learnable else N.dt(x), float(eps),
@@ -133,14 +155,13 @@ def triton_weighted_layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: Op
     x, dy = _rows(x), _rows(dy)
     acc = None if dx_accumulate is None else _rows(dx_accumulate)
     rows, D = x.shape
-    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
+    dx = _new_y(x, D)
     dweight = dbias = ws = None
     lib = N.lib()
     if learnable:
         assert weight is not None and bias is not None
         weight = weight.contiguous()
-        dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
-        dbias = torch.empty((D,), dtype=weight.dtype, device=x.device)
+        dweight, dbias = _new_dparam(x, weight, D), _new_dparam(x, weight, D)
         ws = _workspace(lib.mi355_hstu_layer_norm_bwd_workspace_bytes(rows, D), x.device)
     if wait_event is not None:
         wait_event.wait(torch.cuda.current_stream())
@@ -169,9 +190,7 @@ def triton_layer_norm_mul_dropout_fwd(x: torch.Tensor, u: torch.Tensor, weight: 
     _check_params(weight, bias, D)
     weight, bias = weight.contiguous(), bias.contiguous()
     u, us0, us1, H, UD = _u_layout(u, D)
-    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device)
-    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    y, mean, rstd = _new_y(x, 3 * D if concat_ux else D), _new_stat(x, rows), _new_stat(x, rows)
     if rows == 0:
         return y, mean, rstd, 0, 0, 0
     block_d, num_warps = _launch_params(D, x.element_size())
@@ -199,15 +218,9 @@ def triton_layer_norm_mul_dropout_bwd(dy: torch.Tensor, x: torch.Tensor, u: torc
     _check_params(weight, bias, D)
     weight, bias = weight.contiguous(), bias.contiguous()
     u, us0, us1, H, UD = _u_layout(u, D)
-    if du is None:
-        du = torch.empty_like(u)
-    if du.shape != u.shape or (du.stride(-1) != 1 and du.size(-1) != 1):
-        raise ValueError("du must have the shape of u and a contiguous last dimension")
-    _, ds0, ds1, _, _ = _u_layout(du, D, "du")
-    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device) if compute_y else None
-    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
-    dbias = torch.empty((D,), dtype=weight.dtype, device=x.device)
+    du, ds0, ds1 = _du_layout(du, u, D)
+    y = _new_y(x, 3 * D if concat_ux else D) if compute_y else None
+    dx, dweight, dbias = _new_y(x, D), _new_dparam(x, weight, D), _new_dparam(x, weight, D)
     lib = N.lib()
     ws = _workspace(lib.mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(rows, D), x.device)
     if wait_event is not None:
@@ -304,9 +317,7 @@ def triton_group_norm_mul_dropout_fwd(x: torch.Tensor, u: torch.Tensor, weight: 
     x = _rows(x)
     rows, D = x.shape
     weight, bias = weight.contiguous(), bias.contiguous()
-    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device)
-    mean = torch.empty((rows * num_heads,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((rows * num_heads,), dtype=torch.float32, device=x.device)
+    y, mean, rstd = _new_y(x, 3 * D if concat_ux else D), _new_stat(x, rows * num_heads), _new_stat(x, rows * num_heads)
     if rows == 0:
         return y, mean, rstd, 0, 0, 0, 0
     block_d, block_h, num_warps = _group_launch_params(linear_dim, num_heads, x.element_size())
@@ -332,17 +343,11 @@ def triton_group_norm_mul_dropout_bwd(dy: torch.Tensor, x: torch.Tensor, u: torc
     x, dy = _rows(x), _rows(dy)
     rows, D = x.shape
     weight, bias = weight.contiguous(), bias.contiguous()
-    if du is None:
-        du = torch.empty_like(u)
-    if du.shape != u.shape or (du.stride(-1) != 1 and du.size(-1) != 1):
-        raise ValueError("du must have the shape of u and a contiguous last dimension")
-    _, ds0, ds1, _, _ = _u_layout(du, D, "du")
+    du, ds0, ds1 = _du_layout(du, u, D)
     if du.dim() == 2:
         ds1 = linear_dim
-    y = torch.empty((rows, 3 * D if concat_ux else D), dtype=x.dtype, device=x.device) if compute_y else None
-    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    dweight = torch.empty((num_heads,), dtype=weight.dtype, device=x.device)
-    dbias = torch.empty((num_heads,), dtype=weight.dtype, device=x.device)
+    y = _new_y(x, 3 * D if concat_ux else D) if compute_y else None
+    dx, dweight, dbias = _new_y(x, D), _new_dparam(x, weight, num_heads), _new_dparam(x, weight, num_heads)
     lib = N.lib()
     ws = _workspace(lib.mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(rows, num_heads, linear_dim), x.device)
     N.check(lib.mi355_hstu_gn_mul_dropout_bwd(
@@ -393,9 +398,7 @@ def triton_swish_layer_norm_fwd(x: torch.Tensor, weight: torch.Tensor, bias: tor
     x = _rows(x)
     rows, D = x.shape
     weight, bias = weight.contiguous(), bias.contiguous()
-    y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    y, mean, rstd = _new_y(x, D), _new_stat(x, rows), _new_stat(x, rows)
     N.check(N.lib().mi355_hstu_swish_layer_norm_fwd(
         N.ptr(x), _stride(x), rows, D, N.dt(x), N.ptr(weight), N.ptr(bias), N.dt(weight), float(eps), N.ptr(y), D, N.ptr(mean),
         N.ptr(rstd), N.stream()), "mi355_hstu_swish_layer_norm_fwd")
@@ -412,9 +415,7 @@ def triton_swish_layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch
     x, dy = _rows(x), _rows(dy)
     rows, D = x.shape
     weight, bias = weight.contiguous(), bias.contiguous()
-    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
-    dbias = torch.empty((D,), dtype=weight.dtype, device=x.device)
+    dx, dweight, dbias = _new_y(x, D), _new_dparam(x, weight, D), _new_dparam(x, weight, D)
     lib = N.lib()
     ws = _workspace(lib.mi355_hstu_swish_layer_norm_bwd_workspace_bytes(rows, D), x.device)
     N.check(lib.mi355_hstu_swish_layer_norm_bwd(
@@ -433,8 +434,7 @@ def triton_rms_norm_fwd(x: torch.Tensor, weight: torch.Tensor, eps: float) -> Tu
     x = _rows(x)
     rows, D = x.shape
     weight = weight.contiguous()
-    y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    y, rstd = _new_y(x, D), _new_stat(x, rows)
     N.check(N.lib().mi355_hstu_rms_norm_fwd(
         N.ptr(x), _stride(x), rows, D, N.dt(x), N.ptr(weight), N.dt(weight), float(eps), N.ptr(y), D, N.ptr(rstd), N.stream()),
         "mi355_hstu_rms_norm_fwd")
@@ -450,8 +450,7 @@ def triton_rms_norm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
     x, dy = _rows(x), _rows(dy)
     rows, D = x.shape
     weight = weight.contiguous()
-    dx = torch.empty((rows, D), dtype=x.dtype, device=x.device)
-    dweight = torch.empty((D,), dtype=weight.dtype, device=x.device)
+    dx, dweight = _new_y(x, D), _new_dparam(x, weight, D)
     lib = N.lib()
     ws = _workspace(lib.mi355_hstu_rms_norm_bwd_workspace_bytes(rows, D), x.device)
     N.check(lib.mi355_hstu_rms_norm_bwd(

@@ -227,6 +227,26 @@ def test_symbols_are_exported_and_bound():
     assert lib.mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(0, 8) >= 0
 
 
+def test_workspace_bytes_are_the_contract():
+    """The sizes callers may allocate by: 2 * blocks * D * 4 with blocks = min(ceil(rows / 4), 512) for D <= 2048 and
+    min(rows, 1024) above, at least 1; RMS half of that; the group norm max(fast, general) partial rows plus (c1, c2)."""
+    import mi355_native as N
+
+    lib = N.lib()
+    want = {(1031, 1024): 2113536, (5, 2056): 82240, (100000, 8): 32768, (100000, 4104): 33619968, (0, 8): 64}
+    for (rows, D), nbytes in want.items():
+        assert lib.mi355_hstu_layer_norm_bwd_workspace_bytes(rows, D) == nbytes, (rows, D)
+        assert lib.mi355_hstu_ln_mul_dropout_bwd_workspace_bytes(rows, D) == nbytes, (rows, D)
+        assert lib.mi355_hstu_swish_layer_norm_bwd_workspace_bytes(rows, D) == nbytes, (rows, D)
+    assert lib.mi355_hstu_rms_norm_bwd_workspace_bytes(1031, 1024) == 1056768
+    # (1031, 4, 64): fast 258 blocks, general 1031 slots: (1031 * 4 * 2 + 1031 * 4 * 2) * 4
+    assert lib.mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(1031, 4, 64) == 65984
+    # (67, 257, 8), D = 2056: fast 67 blocks, general 67 slots: (67 * 257 * 2 + 67 * 257 * 2) * 4
+    assert lib.mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(67, 257, 8) == 275504
+    # (100000, 16, 512), D = 8192: the fast layout's rows decide, 1024 blocks against 512 slots: (1024 * 16 * 2 + 100000 * 16 * 2) * 4
+    assert lib.mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(100000, 16, 512) == 12931072
+
+
 def test_bad_arguments_are_error_codes():
     import mi355_native as N
 
