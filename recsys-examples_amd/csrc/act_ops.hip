@@ -124,8 +124,6 @@ __global__ __launch_bounds__(1024) void hstu_silu_dbias_kernel(const float* part
   }
 }
 
-static inline int act_ebytes(int dtype) { return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : 0; }
-
 // row groups of the resident grid, also the number of workspace rows: about 2048 blocks in all when a chunk is 512 columns
 // (16-byte pieces of a 16-bit dtype), at least 64 and at most 2048 row groups, never more than the rows need
 static inline int act_row_blocks(int64_t rows, int64_t N) {
@@ -167,7 +165,7 @@ static void act_launch(int dtype, int v, const ActArgs& a, int gy, hipStream_t s
 }
 
 #define ACT_CHECK_COMMON(NAME, rows, N, dtype)                                                                        \
-  MI355_CHECK_ARG(act_ebytes(dtype) != 0, NAME ": unsupported dtype");                                                \
+  MI355_CHECK_ARG(elem_bytes(dtype) != 0, NAME ": unsupported dtype");                                                \
   MI355_CHECK_ARG(rows >= 0 && rows < ((int64_t)1 << 31) && N >= 0 && N < ((int64_t)1 << 31),                         \
                   NAME ": rows and N must be in 0 .. 2^31")
 
@@ -182,7 +180,7 @@ extern "C" int mi355_hstu_silu_fwd(const void* z, int64_t z_stride, int64_t rows
                   "hstu_silu_fwd: a row stride is not positive or smaller than N");
   if (rows == 0 || N == 0) return MI355_OK;
   MI355_CHECK_ARG(z && s, "hstu_silu_fwd: null buffer with rows > 0");
-  const int eb = act_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   MI355_CHECK_ARG(act_aligned(z, eb) && act_aligned(s, eb), "hstu_silu_fwd: a base pointer is not aligned to the element size");
   if (rows == 1) z_stride = s_stride = N;
   ActVec av{N % (16 / eb) == 0 ? 16 / eb : 1};
@@ -214,8 +212,8 @@ extern "C" int mi355_hstu_silu_bwd(const void* g, int64_t g_stride, const void* 
   if (N == 0) return MI355_OK;
   const bool run = rows > 0;
   MI355_CHECK_ARG(!run || (g && z && dz), "hstu_silu_bwd: null buffer with rows > 0");
-  const int eb = act_ebytes(dtype);
-  MI355_CHECK_ARG(act_aligned(g, eb) && act_aligned(z, eb) && act_aligned(dz, eb) && (!sum || act_aligned(dbias, act_ebytes(dbias_dtype))),
+  const int eb = elem_bytes(dtype);
+  MI355_CHECK_ARG(act_aligned(g, eb) && act_aligned(z, eb) && act_aligned(dz, eb) && (!sum || act_aligned(dbias, elem_bytes(dbias_dtype))),
                   "hstu_silu_bwd: a base pointer is not aligned to the element size");
   if (rows <= 1) g_stride = z_stride = dz_stride = N;
   const int gy = act_row_blocks(rows, N);

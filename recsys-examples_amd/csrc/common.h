@@ -79,6 +79,8 @@ template <> struct Elem<kF16> {
 };
 
 static inline size_t dtype_bytes(int dt) { return dt == kF32 ? 4 : 2; }
+// bytes of an element of a dtype code an entry point was handed, 0 for a code that is none of the three
+static inline int elem_bytes(int dtype) { return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : 0; }
 
 // load 4 consecutive elements as fp32 (16 B for f32, 8 B for 16-bit types)
 template <int DT>

@@ -22,10 +22,9 @@
 // not seen by the polls of a graph replay -- suspected, not pursued: the node's zeros are still in flight or in a cache that
 // the polls' device-scope loads do not look in when the scan starts -- so the look-back does not lean on one).
 //
-// Padded dense (mi355_jagged_to_padded, mi355_padded_to_jagged).  One wave per run of 2^k rows of the OUTPUT (k as the concat
-// chooses it, jagged_dev.h): lane l resolves row l of the run (a division for the dense side, a binary search of the offsets
-// for the jagged side) into a source address or "fill", then the run is copied as one stream of pieces of W bytes (W the
-// widest of 16 / 8 / 4 / 2 that divides the row, every base pointer and every stride), four loads in flight per lane.  Every
+// Padded dense (mi355_jagged_to_padded, mi355_padded_to_jagged).  The row run of jagged_dev.h over the rows of the OUTPUT, moved by
+// its wave_move_run in the fill form.  Their own is the resolve step: a division for the dense side, a binary search of the
+// offsets for the jagged side, into a source address or "fill"; the strides of the dense side count for the access width.  Every
 // output element is written exactly once, the fill included: there is no memset.
 //
 // Select (mi355_kjt_select_lengths / _values).  Output bag (f, j) is input bag (f, indices[j]).  The values kernel gives every
@@ -229,69 +228,6 @@ __global__ __launch_bounds__(kScanThreads) void cumsum_kernel(const ScanArgs a) 
 // ---------------------------------------------------------------------------------------------------------------------
 // jagged <-> padded dense
 // ---------------------------------------------------------------------------------------------------------------------
-static __device__ __attribute__((aligned(16))) uint32_t g_fj_zero[4];
-
-template <int W> struct FjPiece { typedef typename Words<W / 4>::T T; };
-template <> struct FjPiece<2> { typedef uint16_t T; };
-
-struct FillBits { uint32_t w[4]; };   // the padding element repeated over 16 bytes
-
-template <int W>
-__device__ __forceinline__ typename FjPiece<W>::T fill_piece(const FillBits& f) {
-  typename FjPiece<W>::T v;
-  if constexpr (W == 16) { v[0] = f.w[0]; v[1] = f.w[1]; v[2] = f.w[2]; v[3] = f.w[3]; }
-  else if constexpr (W == 8) { v[0] = f.w[0]; v[1] = f.w[1]; }
-  else if constexpr (W == 4) v = f.w[0];
-  else v = (uint16_t)f.w[0];
-  return v;
-}
-
-// The wave writes `nrows` rows of `vpr` pieces of W bytes: lane l holds the destination address of row l (0: not written) and
-// its source address (0: the row is the fill).  Loads are unconditional (a fill row reads a zero word), as in jagged_ops.hip.
-template <int W>
-__device__ __forceinline__ void wave_move_run(uintptr_t src, uintptr_t dst, int nrows, uint32_t vpr, int vpr_shift,
-                                              const FillBits& fill) {
-  typedef typename FjPiece<W>::T V;
-  typedef const __attribute__((address_space(1))) V* gsrc_t;
-  typedef __attribute__((address_space(1))) V* gdst_t;
-  constexpr int UN = 4;
-  const uint32_t lane = (uint32_t)lane_id();
-  const uint32_t total = (uint32_t)nrows * vpr;
-  const uintptr_t zero = (uintptr_t)g_fj_zero;
-  const V fv = fill_piece<W>(fill);
-  for (uint32_t base = 0; base < total; base += 64 * UN) {
-    V v[UN];
-    uintptr_t d[UN];
-    bool copy[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const uint32_t i = base + u * 64 + lane;
-      const bool in = i < total;
-      const uint32_t ic = in ? i : 0u;
-      const uint32_t row = vpr_shift >= 0 ? ic >> vpr_shift : ic / vpr;
-      const uintptr_t col = (uintptr_t)(ic - row * vpr) * W;
-      const uintptr_t s = shfl_addr(src, (int)row), dd = shfl_addr(dst, (int)row);
-      copy[u] = in && s != 0;
-      v[u] = *(gsrc_t)(copy[u] ? s + col : zero);
-      d[u] = in && dd != 0 ? dd + col : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u)
-      if (d[u]) *(gdst_t)d[u] = copy[u] ? v[u] : fv;
-  }
-}
-
-// largest b in [0, B - 1] with off[b] <= m (sample_of of jagged_dev.h for either offsets type)
-template <typename OT>
-__device__ __forceinline__ int64_t sample_of_t(const OT* off, int64_t B, int64_t m) {
-  int64_t lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if ((int64_t)off[mid] <= m) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 struct PadArgs {
   uintptr_t jagged;       // [T, D] rows of row_bytes
   uintptr_t dense;        // [B, N, D]: element (b, l) at dense + b stride_b + l stride_n (bytes)
@@ -299,21 +235,17 @@ struct PadArgs {
   int64_t T, B, N;
   int64_t stride_b, stride_n;
   int64_t out_rows;       // B N (to padded) or the jagged row count (to jagged)
-  uint32_t row_bytes, vpr;
-  int vpr_shift, rpw_log2;
+  uint32_t row_bytes;
+  RunPlan plan;
   FillBits fill;
 };
 
 template <int W, typename OT>
 __global__ __launch_bounds__(256) void jagged_to_padded_kernel(const PadArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.out_rows) return;   // (wave-uniform)
-  const int64_t left = a.out_rows - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.out_rows, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   const int64_t b = m / a.N, l = m - b * a.N;
   const OT* off = (const OT*)a.offsets;
   const int64_t s = (int64_t)off[b], len = (int64_t)off[b + 1] - s;
@@ -321,29 +253,25 @@ __global__ __launch_bounds__(256) void jagged_to_padded_kernel(const PadArgs a) 
   const bool real = have && l < len && r >= 0 && r < a.T;
   const uintptr_t src = real ? a.jagged + (uintptr_t)r * a.row_bytes : 0;
   const uintptr_t dst = have ? a.dense + (uintptr_t)m * a.row_bytes : 0;
-  wave_move_run<W>(src, dst, nrows, a.vpr, a.vpr_shift, a.fill);
+  wave_move_run<W, true>(src, dst, run.nrows, a.plan.vpr, a.plan.vpr_shift, a.fill);
 }
 
 template <int W, typename OT>
 __global__ __launch_bounds__(256) void padded_to_jagged_kernel(const PadArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.out_rows) return;   // (wave-uniform)
-  const int64_t left = a.out_rows - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.out_rows, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   uintptr_t src = 0;
   if (a.B > 0) {
     const OT* off = (const OT*)a.offsets;
-    const int64_t b = sample_of_t<OT>(off, a.B, m);
+    const int64_t b = sample_of<OT>(off, a.B, m);
     const int64_t l = m - (int64_t)off[b];
     if (have && l >= 0 && l < a.N && m < (int64_t)off[b + 1])
       src = a.dense + (uintptr_t)b * (uintptr_t)a.stride_b + (uintptr_t)l * (uintptr_t)a.stride_n;
   }
   const uintptr_t dst = have ? a.jagged + (uintptr_t)m * a.row_bytes : 0;
-  wave_move_run<W>(src, dst, nrows, a.vpr, a.vpr_shift, a.fill);
+  wave_move_run<W, true>(src, dst, run.nrows, a.plan.vpr, a.plan.vpr_shift, a.fill);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -383,7 +311,7 @@ __global__ __launch_bounds__(256) void kjt_select_values_kernel(const SelArgs a)
   if (p >= a.total) return;
   const PT* po = (const PT*)a.out_offsets;
   const int64_t bags = a.F * a.S;
-  const int64_t bag = sample_of_t<PT>(po, bags, p);   // the last bag that starts at or before p: the one that holds it
+  const int64_t bag = sample_of<PT>(po, bags, p);   // the last bag that starts at or before p: the one that holds it
   const int64_t k = p - (int64_t)po[bag];
   const int64_t f = bag / a.S, j = bag - f * a.S;
   const int64_t idx = (int64_t)((const IT*)a.indices)[j];
@@ -404,10 +332,6 @@ __global__ __launch_bounds__(256) void kjt_select_values_kernel(const SelArgs a)
   }
 }
 
-static inline int fj_access_width(uint64_t bits) {
-  return (bits & 15) == 0 ? 16 : (bits & 7) == 0 ? 8 : (bits & 3) == 0 ? 4 : 2;
-}
-
 static inline FillBits fill_bits(uint64_t pattern, int eb) {
   FillBits f;
   if (eb == 8) { f.w[0] = f.w[2] = (uint32_t)pattern; f.w[1] = f.w[3] = (uint32_t)(pattern >> 32); }
@@ -421,22 +345,6 @@ static inline FillBits fill_bits(uint64_t pattern, int eb) {
 }  // namespace mi355
 
 using namespace mi355;
-
-#define MI355_FJ_LAUNCH_W(KERNEL, OT, W, grid, stream, args)                                          \
-  do {                                                                                                \
-    switch (W) {                                                                                      \
-      case 16: hipLaunchKernelGGL((KERNEL<16, OT>), dim3(grid), dim3(256), 0, stream, args); break;   \
-      case 8: hipLaunchKernelGGL((KERNEL<8, OT>), dim3(grid), dim3(256), 0, stream, args); break;     \
-      case 4: hipLaunchKernelGGL((KERNEL<4, OT>), dim3(grid), dim3(256), 0, stream, args); break;     \
-      default: hipLaunchKernelGGL((KERNEL<2, OT>), dim3(grid), dim3(256), 0, stream, args); break;    \
-    }                                                                                                 \
-  } while (0)
-
-#define MI355_FJ_LAUNCH(KERNEL, itype, W, grid, stream, args)                                         \
-  do {                                                                                                \
-    if (itype == 1) MI355_FJ_LAUNCH_W(KERNEL, int64_t, W, grid, stream, args);                        \
-    else MI355_FJ_LAUNCH_W(KERNEL, int32_t, W, grid, stream, args);                                   \
-  } while (0)
 
 static inline bool itype_ok(int t) { return t == 0 || t == 1; }
 
@@ -505,15 +413,22 @@ extern "C" int mi355_cumsum(const void* in, void* out, int64_t rows, int64_t n, 
   return MI355_OK;
 }
 
-static int pad_common(PadArgs& a, int64_t D, int elem_bytes, uint64_t align_bits, int64_t out_rows) {
-  const uint64_t rb = (uint64_t)D * elem_bytes;
-  const int W = fj_access_width(rb | align_bits);
+// the end of both entry points: the access width, the run plan and the launch
+static int pad_launch(bool to_padded, const char* name, PadArgs& a, int64_t D, int eb, uint64_t align_bits, int64_t out_rows,
+                      int itype, hipStream_t stream) {
+  const uint64_t rb = (uint64_t)D * eb;
+  const int w = access_width(rb | align_bits);
   a.row_bytes = (uint32_t)rb;
-  a.vpr = (uint32_t)(rb / W);
-  a.vpr_shift = log2_or_minus1(a.vpr);
-  a.rpw_log2 = rows_per_wave_log2(out_rows, rb);
   a.out_rows = out_rows;
-  return W;
+  unsigned grid;
+  if (const int rc = plan_run(out_rows, rb, rb / w, name, a.plan, grid)) return rc;
+#define MI355_PAD_GO(OT)                                                                                        \
+  MI355_SWITCH_W(w, if (to_padded) jagged_to_padded_kernel<W, OT><<<dim3(grid), dim3(256), 0, stream>>>(a);     \
+                    else padded_to_jagged_kernel<W, OT><<<dim3(grid), dim3(256), 0, stream>>>(a))
+  if (itype == 1) { MI355_PAD_GO(int64_t) } else { MI355_PAD_GO(int32_t) }
+#undef MI355_PAD_GO
+  MI355_LAUNCH_CHECK();
+  return MI355_OK;
 }
 
 extern "C" int mi355_jagged_to_padded(const void* values, int64_t T, const void* offsets, int offsets_itype, int64_t B,
@@ -534,12 +449,7 @@ extern "C" int mi355_jagged_to_padded(const void* values, int64_t T, const void*
   a.jagged = (uintptr_t)values; a.dense = (uintptr_t)out; a.offsets = offsets;
   a.T = values ? T : 0; a.B = B; a.N = max_len;
   a.fill = fill_bits(padding_bits, elem_bytes);
-  const int W = pad_common(a, D, elem_bytes, bits, out_rows);
-  const int64_t grid = ceil_div(ceil_div(out_rows, (int64_t)1 << a.rpw_log2), 4);
-  MI355_CHECK_ARG(grid < ((int64_t)1 << 31), "jagged_to_padded: too many rows for one launch");
-  MI355_FJ_LAUNCH(jagged_to_padded_kernel, offsets_itype, W, (unsigned)grid, stream, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return pad_launch(true, "jagged_to_padded", a, D, elem_bytes, bits, out_rows, offsets_itype, stream);
 }
 
 extern "C" int mi355_padded_to_jagged(const void* dense, int64_t stride_b, int64_t stride_n, int64_t B, int64_t N,
@@ -564,12 +474,7 @@ extern "C" int mi355_padded_to_jagged(const void* dense, int64_t stride_b, int64
   a.B = any ? B : 0; a.N = N;
   a.stride_b = stride_b * elem_bytes; a.stride_n = stride_n * elem_bytes;
   a.fill = fill_bits(0, elem_bytes);
-  const int W = pad_common(a, D, elem_bytes, bits, total);
-  const int64_t grid = ceil_div(ceil_div(total, (int64_t)1 << a.rpw_log2), 4);
-  MI355_CHECK_ARG(grid < ((int64_t)1 << 31), "padded_to_jagged: too many rows for one launch");
-  MI355_FJ_LAUNCH(padded_to_jagged_kernel, offsets_itype, W, (unsigned)grid, stream, a);
-  MI355_LAUNCH_CHECK();
-  return MI355_OK;
+  return pad_launch(false, "padded_to_jagged", a, D, elem_bytes, bits, total, offsets_itype, stream);
 }
 
 extern "C" int mi355_kjt_select_lengths(const void* lengths, int lengths_itype, const void* indices, int indices_itype,

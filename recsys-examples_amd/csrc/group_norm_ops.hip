@@ -480,7 +480,7 @@ extern "C" int mi355_hstu_gn_mul_dropout_fwd(const void* x, int64_t x_stride, co
                   "hstu_gn_mul_dropout_fwd: a stride is smaller than the extent it steps over");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(x && u && y && weight && bias && mean && rstd, "hstu_gn_mul_dropout_fwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(x, eb) && norm_aligned(u, eb) && norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web),
                   "hstu_gn_mul_dropout_fwd: a base pointer is not aligned to the element size");
   MI355_CHECK_ARG((H - 1) * u_stride1 * eb < ((int64_t)1 << 31), "hstu_gn_mul_dropout_fwd: u head stride too large");
@@ -529,7 +529,7 @@ extern "C" int mi355_hstu_gn_mul_dropout_bwd(const void* dy, int64_t dy_stride, 
   MI355_CHECK_ARG(rows == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 &&
                                 workspace_bytes >= mi355_hstu_gn_mul_dropout_bwd_workspace_bytes(rows, H, L)),
                   "hstu_gn_mul_dropout_bwd: workspace is null, not 16-byte aligned or too small");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(dy, eb) && norm_aligned(x, eb) && norm_aligned(u, eb) && norm_aligned(dx, eb) && norm_aligned(du, eb) &&
                       norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web) && norm_aligned(dweight, web) &&
                       norm_aligned(dbias, web),

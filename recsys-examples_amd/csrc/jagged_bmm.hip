@@ -484,7 +484,6 @@ __global__ __launch_bounds__(1024) void jagged_row_sum_kernel(const JsumArgs a) 
   }
 }
 
-static inline int jb_ebytes(int dtype) { return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : 0; }
 static inline bool jb_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool jb_al16(int64_t bytes) { return (bytes & 15) == 0; }
 // the stride of a single row (or a single sample) is never used
@@ -495,7 +494,7 @@ static inline bool jb_stride_ok(int64_t count, int64_t width, int64_t stride) { 
 using namespace mi355;
 
 #define JB_CHECK_COMMON(NAME, dtype, batch, L, offsets)                                                   \
-  MI355_CHECK_ARG(jb_ebytes(dtype) != 0, NAME ": unsupported dtype");                                     \
+  MI355_CHECK_ARG(elem_bytes(dtype) != 0, NAME ": unsupported dtype");                                    \
   MI355_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 31), NAME ": batch must be in 1 .. 2^31");         \
   MI355_CHECK_ARG(L >= 0 && L < ((int64_t)1 << 34), NAME ": rows must be in 0 .. 2^34");                  \
   MI355_CHECK_ARG(offsets != nullptr, NAME ": null offsets")
@@ -527,7 +526,7 @@ extern "C" int mi355_jagged_dense_bmm(const void* jagged, int64_t jagged_stride,
   MI355_CHECK_ARG(!bias || jb_stride_ok(batch, N, bias_stride), "jagged_dense_bmm: the stride of bias is smaller than N");
   if (L == 0) return MI355_OK;
   MI355_CHECK_ARG(jagged && dense && out, "jagged_dense_bmm: null buffer with rows > 0");
-  const int eb = jb_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   MI355_CHECK_ARG((((uintptr_t)jagged | (uintptr_t)dense | (uintptr_t)bias | (uintptr_t)out) & (uintptr_t)(eb - 1)) == 0,
                   "jagged_dense_bmm: a base pointer is not aligned to the element size");
   JbmmArgs a{};
@@ -556,7 +555,7 @@ extern "C" int mi355_jagged_row_sum(const void* jagged, int64_t jagged_stride, c
                   "jagged_row_sum: a row stride is smaller than the width");
   MI355_CHECK_ARG(out != nullptr, "jagged_row_sum: null out");
   MI355_CHECK_ARG(L == 0 || jagged, "jagged_row_sum: null buffer with rows > 0");
-  const int eb = jb_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   MI355_CHECK_ARG((((uintptr_t)jagged | (uintptr_t)out) & (uintptr_t)(eb - 1)) == 0,
                   "jagged_row_sum: a base pointer is not aligned to the element size");
   JsumArgs a{};
@@ -599,7 +598,7 @@ extern "C" int mi355_jagged_jagged_bmm(const void* a_rows, int64_t a_stride, con
   MI355_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 &&
                   workspace_bytes >= mi355_jagged_jagged_bmm_workspace_bytes(batch, L, M, N),
                   "jagged_jagged_bmm: workspace is null, not 16-byte aligned or too small");
-  const int eb = jb_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   MI355_CHECK_ARG((((uintptr_t)a_rows | (uintptr_t)b_rows | (uintptr_t)out | (uintptr_t)col_sum) & (uintptr_t)(eb - 1)) == 0,
                   "jagged_jagged_bmm: a base pointer is not aligned to the element size");
   JjArgs a{};
@@ -634,7 +633,7 @@ extern "C" int mi355_jagged_broadcast_add(const void* jagged, int64_t jagged_str
                   "jagged_broadcast_add: a row stride is smaller than the width");
   if (L == 0) return MI355_OK;
   MI355_CHECK_ARG(jagged && dense && out, "jagged_broadcast_add: null buffer with rows > 0");
-  const int eb = jb_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   MI355_CHECK_ARG((((uintptr_t)jagged | (uintptr_t)dense | (uintptr_t)out) & (uintptr_t)(eb - 1)) == 0,
                   "jagged_broadcast_add: a base pointer is not aligned to the element size");
   JaddArgs a{};

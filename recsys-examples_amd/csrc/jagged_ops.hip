@@ -6,19 +6,14 @@
 // hstu_inference_preprocess (jagged_tensor_op_cuda.cpp:135-240).  Written for wave64 from the semantics; the reference's
 // kernels give a 32-lane warp to a row and index rows in 32 bits.
 //
-// Decomposition.  The unit of work is a run of 2^k consecutive rows of the MERGED buffer (k = 2 .. 6, chosen per call so that
-// a small call still fills the chip), one wave per run -- load follows the bytes, never the length of one sample (a 4096-row
-// sample next to empty ones is 64 .. 1024 waves like any other 4096 rows).  A wave works in two phases:
-//   resolve: lane l owns row m0 + l.  Binary search of merged_offsets for its sample, then one pass over the n tensors'
-//            offsets (the tensor index is wave-uniform: the pointer tables are kernel arguments read with scalar loads, the
-//            offsets vector loads that mostly share a cache line) -> the address of its row in its tensor.
-//   copy:    the run is one flat stream of row_bytes / W pieces of W bytes; lane i of a step takes piece i, its row's two
-//            addresses come from the owning lane with shuffles.  Four steps' loads are issued before their stores.  All
-//            lanes work whatever D is (D = 136 bf16: 17 pieces per row).  Loads are unconditional (idle lanes read a zero
-//            word), so hipcc does not fence each of them into its own branch (gather_dev.h, g_zero_row).
-// W is the widest of 16 / 8 / 4 / 2 bytes that divides the row AND every base pointer of the call; the host checks the
-// pointers, not only D.  Everything is addressed in 64 bits.  The backward is the same kernel with source and destination
-// swapped: every row of every per-tensor buffer is some merged row, so every one is written.
+// The decomposition -- one wave per run of 2^k rows of the MERGED buffer, lane l resolves row l, the run is copied as one flat
+// stream of pieces -- is the row run of jagged_dev.h, and so are the piece loop and the choice of k and W.  Here is the resolve
+// step of the two ops:
+//   concat:     binary search of merged_offsets for the row's sample, then one pass over the n tensors' offsets (the tensor index
+//               is wave-uniform: the pointer tables are kernel arguments read with scalar loads, the offsets vector loads that
+//               mostly share a cache line) -> the address of its row in its tensor.  The backward is the same kernel with source
+//               and destination swapped: every row of every per-tensor buffer is some merged row, so every one is written.
+//   preprocess: the row's place in the item / action interleave of its sample (below).
 // No row outside a tensor is touched whatever the offsets hold: a row index outside [0, rows[t]) or [0, total_rows) is
 // skipped.
 #include "common.h"
@@ -39,11 +34,9 @@ struct JagArgs {
   int64_t total_rows;
   int64_t B;
   uint32_t row_bytes;
-  uint32_t vpr;                    // pieces per row = row_bytes / W
-  int vpr_shift;                   // log2(vpr) when it is a power of two, else -1
   int n;
   int dir;                         // 0: tensors -> merged, 1: merged -> tensors
-  int rpw_log2;                    // rows per wave
+  RunPlan plan;                     // pieces of W bytes
 };
 
 struct PreArgs {
@@ -52,8 +45,8 @@ struct PreArgs {
   const int64_t* action_offsets;   // [B + 1]
   const int64_t* out_offsets;      // [B + 1]
   int64_t item_rows, action_rows, out_rows, B;
-  uint32_t row_bytes, vpr;
-  int vpr_shift, rpw_log2;
+  uint32_t row_bytes;
+  RunPlan plan;
 };
 
 struct WorkArgs {
@@ -63,55 +56,12 @@ struct WorkArgs {
   int n;
 };
 
-static __device__ __attribute__((aligned(16))) uint32_t g_jag_zero[4];
-
-template <int W> struct Piece;
-template <> struct Piece<16> { typedef unsigned int T __attribute__((ext_vector_type(4))); };
-template <> struct Piece<8> { typedef unsigned int T __attribute__((ext_vector_type(2))); };
-template <> struct Piece<4> { typedef unsigned int T; };
-template <> struct Piece<2> { typedef unsigned short T; };
-
-// The wave copies `nrows` rows of `vpr` pieces of W bytes: lane l holds the source and destination address of row l (0: skip it).
-template <int W>
-__device__ __forceinline__ void wave_copy_run(uintptr_t src, uintptr_t dst, int nrows, uint32_t vpr, int vpr_shift) {
-  typedef typename Piece<W>::T V;
-  typedef const __attribute__((address_space(1))) V* gsrc_t;
-  typedef __attribute__((address_space(1))) V* gdst_t;
-  constexpr int UN = 4;
-  const uint32_t lane = (uint32_t)lane_id();
-  const uint32_t total = (uint32_t)nrows * vpr;
-  const uintptr_t zero = (uintptr_t)g_jag_zero;
-  for (uint32_t base = 0; base < total; base += 64 * UN) {
-    V v[UN];
-    uintptr_t d[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const uint32_t i = base + u * 64 + lane;
-      const bool in = i < total;
-      const uint32_t ic = in ? i : 0u;
-      const uint32_t row = vpr_shift >= 0 ? ic >> vpr_shift : ic / vpr;
-      const uintptr_t col = (uintptr_t)(ic - row * vpr) * W;
-      const uintptr_t s = shfl_addr(src, (int)row), dd = shfl_addr(dst, (int)row);
-      const bool ok = in && s != 0 && dd != 0;
-      v[u] = *(gsrc_t)(ok ? s + col : zero);
-      d[u] = ok ? dd + col : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u)
-      if (d[u]) *(gdst_t)d[u] = v[u];
-  }
-}
-
 template <int W>
 __global__ __launch_bounds__(256) void jagged_concat_kernel(const JagArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.total_rows) return;   // (wave-uniform)
-  const int64_t left = a.total_rows - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.total_rows, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   const int64_t b = sample_of(a.merged_offsets, a.B, m);
   int64_t rem = m - a.merged_offsets[b];
   bool open = have && rem >= 0;
@@ -129,21 +79,17 @@ __global__ __launch_bounds__(256) void jagged_concat_kernel(const JagArgs a) {
     rem -= len;
   }
   const uintptr_t mrow = trow ? a.merged + (uintptr_t)m * a.row_bytes : 0;
-  wave_copy_run<W>(a.dir == 0 ? trow : mrow, a.dir == 0 ? mrow : trow, nrows, a.vpr, a.vpr_shift);
+  wave_move_run<W, false>(a.dir == 0 ? trow : mrow, a.dir == 0 ? mrow : trow, run.nrows, a.plan.vpr, a.plan.vpr_shift);
 }
 
 // Output row r of a sample with I items, A actions (A - I = e in {0, 1}) and L = 2 h + e + C output rows:
 //   r < e: action[0];  r' = r - e < 2 h: item[r' / 2] (even) or action[r' / 2 + e] (odd);  else item[h + r' - 2 h].
 template <int W>
 __global__ __launch_bounds__(256) void hstu_inference_preprocess_kernel(const PreArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.out_rows) return;
-  const int64_t left = a.out_rows - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.out_rows, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   const int64_t b = sample_of(a.out_offsets, a.B, m);
   const int64_t o0 = a.out_offsets[b], L = a.out_offsets[b + 1] - o0;
   const int64_t i0 = a.item_offsets[b], I = a.item_offsets[b + 1] - i0;
@@ -160,7 +106,7 @@ __global__ __launch_bounds__(256) void hstu_inference_preprocess_kernel(const Pr
   const bool ok = have && r >= 0 && r < L && k >= 0 && k < cnt && g >= 0 && g < (from_action ? a.action_rows : a.item_rows);
   const uintptr_t src = ok ? (from_action ? a.action : a.item) + (uintptr_t)g * a.row_bytes : 0;
   const uintptr_t dst = ok ? a.out + (uintptr_t)m * a.row_bytes : 0;
-  wave_copy_run<W>(src, dst, nrows, a.vpr, a.vpr_shift);
+  wave_move_run<W, false>(src, dst, run.nrows, a.plan.vpr, a.plan.vpr_shift);
 }
 
 // work_id = (b n + t) nb + idx -> rows of block idx of segment (b, t); blockIdx.y = t keeps the table index wave-uniform
@@ -175,29 +121,11 @@ __global__ __launch_bounds__(256) void jagged_block_workloads_kernel(const WorkA
   a.out[(b * a.n + t) * a.nb + idx] = w > 0 ? w : 0;
 }
 
-static inline int elem_bytes_of(int dtype) {
-  return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : dtype == kJagF64 ? 8 : 0;
-}
-
-// widest access that divides the row and every address in `align_bits` (the OR of the base pointers)
-static inline int access_width(uint64_t row_bytes, uintptr_t align_bits) {
-  const uint64_t x = row_bytes | (uint64_t)align_bits;
-  return (x & 15) == 0 ? 16 : (x & 7) == 0 ? 8 : (x & 3) == 0 ? 4 : 2;
-}
+static inline int elem_bytes_of(int dtype) { return dtype == kJagF64 ? 8 : elem_bytes(dtype); }
 
 }  // namespace mi355
 
 using namespace mi355;
-
-#define MI355_JAG_LAUNCH(KERNEL, W, grid, stream, args)                                           \
-  do {                                                                                            \
-    switch (W) {                                                                                  \
-      case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(256), 0, stream, args); break;     \
-      case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(256), 0, stream, args); break;       \
-      case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(256), 0, stream, args); break;       \
-      default: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(256), 0, stream, args); break;      \
-    }                                                                                             \
-  } while (0)
 
 extern "C" int mi355_jagged_concat(int n, const void* const* values, const int64_t* const* offsets, const int64_t* rows,
                                    int64_t batch, const int64_t* merged_offsets, void* merged, int64_t total_rows, int64_t D,
@@ -224,20 +152,17 @@ extern "C" int mi355_jagged_concat(int n, const void* const* values, const int64
   MI355_CHECK_ARG((bits & (uintptr_t)(eb - 1)) == 0, "jagged_concat: a base pointer is not aligned to the element size");
   if (total_rows == 0) return MI355_OK;
   const uint64_t rb = (uint64_t)D * eb;
-  const int W = access_width(rb, bits);
+  const int w = access_width(rb | bits);
   a.merged_offsets = merged_offsets;
   a.merged = (uintptr_t)merged;
   a.total_rows = total_rows;
   a.B = batch;
   a.row_bytes = (uint32_t)rb;
-  a.vpr = (uint32_t)(rb / W);
-  a.vpr_shift = log2_or_minus1(a.vpr);
   a.n = n;
   a.dir = direction;
-  a.rpw_log2 = rows_per_wave_log2(total_rows, rb);
-  const int64_t grid = ceil_div(ceil_div(total_rows, (int64_t)1 << a.rpw_log2), 4);
-  MI355_CHECK_ARG(grid < ((int64_t)1 << 31), "jagged_concat: too many rows for one launch");
-  MI355_JAG_LAUNCH(jagged_concat_kernel, W, (unsigned)grid, stream, a);
+  unsigned grid;
+  if (const int rc = plan_run(total_rows, rb, rb / w, "jagged_concat", a.plan, grid)) return rc;
+  MI355_SWITCH_W(w, jagged_concat_kernel<W><<<dim3(grid), dim3(256), 0, stream>>>(a));
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }
@@ -283,18 +208,15 @@ extern "C" int mi355_hstu_inference_preprocess(const void* item_values, int64_t 
   MI355_CHECK_ARG((bits & (uintptr_t)(eb - 1)) == 0, "hstu_inference_preprocess: a base pointer is not aligned to the element size");
   if (out_rows == 0) return MI355_OK;
   const uint64_t rb = (uint64_t)D * eb;
-  const int W = access_width(rb, bits);
+  const int w = access_width(rb | bits);
   PreArgs a{};
   a.item = (uintptr_t)item_values; a.action = (uintptr_t)action_values; a.out = (uintptr_t)out;
   a.item_offsets = item_offsets; a.action_offsets = action_offsets; a.out_offsets = out_offsets;
   a.item_rows = item_rows; a.action_rows = action_rows; a.out_rows = out_rows; a.B = batch;
   a.row_bytes = (uint32_t)rb;
-  a.vpr = (uint32_t)(rb / W);
-  a.vpr_shift = log2_or_minus1(a.vpr);
-  a.rpw_log2 = rows_per_wave_log2(out_rows, rb);
-  const int64_t grid = ceil_div(ceil_div(out_rows, (int64_t)1 << a.rpw_log2), 4);
-  MI355_CHECK_ARG(grid < ((int64_t)1 << 31), "hstu_inference_preprocess: too many rows for one launch");
-  MI355_JAG_LAUNCH(hstu_inference_preprocess_kernel, W, (unsigned)grid, stream, a);
+  unsigned grid;
+  if (const int rc = plan_run(out_rows, rb, rb / w, "hstu_inference_preprocess", a.plan, grid)) return rc;
+  MI355_SWITCH_W(w, hstu_inference_preprocess_kernel<W><<<dim3(grid), dim3(256), 0, stream>>>(a));
   MI355_LAUNCH_CHECK();
   return MI355_OK;
 }

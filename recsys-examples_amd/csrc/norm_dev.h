@@ -466,8 +466,6 @@ __global__ __launch_bounds__(1024) void hstu_norm_dwdb_kernel(const float* parti
 }
 
 // ---- host ----
-static inline int norm_ebytes(int dtype) { return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : 0; }
-
 // the elements of one access: 16 bytes' worth, or 1 as soon as a base pointer or a stride is not a multiple of 16 bytes
 struct NormVec {
   int v;
@@ -548,7 +546,7 @@ static inline void norm_set_dropout(NormDropout& a, double p, int training, uint
 // WEIGHTS: how the message names them, "weight and bias are" or "weights are"
 #define NORM_CHECK_COMMON(NAME, rows, D, dtype, wdtype, WEIGHTS)                                             \
   MI355_CHECK_ARG(D > 0 && D <= kNormMaxD, NAME ": D must be in 1 .. 8192");                                 \
-  MI355_CHECK_ARG(norm_ebytes(dtype) != 0, NAME ": unsupported dtype");                                      \
+  MI355_CHECK_ARG(elem_bytes(dtype) != 0, NAME ": unsupported dtype");                                       \
   MI355_CHECK_ARG(wdtype == kF32 || wdtype == dtype, NAME ": " WEIGHTS " fp32 or have the dtype of the rows"); \
   MI355_CHECK_ARG(rows >= 0 && rows < ((int64_t)1 << 31), NAME ": rows must be in 0 .. 2^31")
 

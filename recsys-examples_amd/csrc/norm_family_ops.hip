@@ -23,7 +23,7 @@ template <int KIND>
 static int fam_fwd(const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype, const void* weight,
                    const void* bias, int weight_dtype, float eps, void* y, int64_t y_stride, float* mean, float* rstd,
                    hipStream_t stream) {
-  const int eb = norm_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   NormVec nv{D % (16 / eb) == 0 ? 16 / eb : 1};
   nv.need(x, x_stride * eb); nv.need(y, y_stride * eb); nv.need(weight, 0); nv.need(bias, 0);
   NormArgs a{};
@@ -39,7 +39,7 @@ template <int KIND>
 static int fam_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, int64_t rows, int64_t D, int dtype,
                    const void* weight, const void* bias, int weight_dtype, const float* mean, const float* rstd, void* dx,
                    int64_t dx_stride, void* dweight, void* dbias, void* workspace, hipStream_t stream) {
-  const int eb = norm_ebytes(dtype);
+  const int eb = elem_bytes(dtype);
   NormVec nv{D % (16 / eb) == 0 ? 16 / eb : 1};
   nv.need(dy, dy_stride * eb); nv.need(x, x_stride * eb); nv.need(dx, dx_stride * eb); nv.need(weight, 0); nv.need(bias, 0);
   NormArgs a{};
@@ -62,7 +62,7 @@ extern "C" int mi355_hstu_swish_layer_norm_fwd(const void* x, int64_t x_stride, 
   MI355_CHECK_ARG(x_stride >= D && y_stride >= D, "hstu_swish_layer_norm_fwd: a row stride is smaller than D");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(x && y && weight && bias && mean && rstd, "hstu_swish_layer_norm_fwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(x, eb) && norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web),
                   "hstu_swish_layer_norm_fwd: a base pointer is not aligned to the element size");
   return fam_fwd<kNormSwish>(x, x_stride, rows, D, dtype, weight, bias, weight_dtype, eps, y, y_stride, mean, rstd, stream);
@@ -88,7 +88,7 @@ extern "C" int mi355_hstu_swish_layer_norm_bwd(const void* dy, int64_t dy_stride
   MI355_CHECK_ARG(rows == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 &&
                                 workspace_bytes >= mi355_hstu_swish_layer_norm_bwd_workspace_bytes(rows, D)),
                   "hstu_swish_layer_norm_bwd: workspace is null, not 16-byte aligned or too small");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(dy, eb) && norm_aligned(x, eb) && norm_aligned(dx, eb) && norm_aligned(weight, web) &&
                       norm_aligned(bias, web) && norm_aligned(dweight, web) && norm_aligned(dbias, web),
                   "hstu_swish_layer_norm_bwd: a base pointer is not aligned to the element size");
@@ -102,7 +102,7 @@ extern "C" int mi355_hstu_rms_norm_fwd(const void* x, int64_t x_stride, int64_t 
   MI355_CHECK_ARG(x_stride >= D && y_stride >= D, "hstu_rms_norm_fwd: a row stride is smaller than D");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(x && y && weight && rstd, "hstu_rms_norm_fwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(x, eb) && norm_aligned(y, eb) && norm_aligned(weight, web),
                   "hstu_rms_norm_fwd: a base pointer is not aligned to the element size");
   return fam_fwd<kNormRms>(x, x_stride, rows, D, dtype, weight, nullptr, weight_dtype, eps, y, y_stride, nullptr, rstd, stream);
@@ -119,7 +119,7 @@ extern "C" int mi355_hstu_rms_norm_bwd(const void* dy, int64_t dy_stride, const 
   MI355_CHECK_ARG(rows == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 &&
                                 workspace_bytes >= mi355_hstu_rms_norm_bwd_workspace_bytes(rows, D)),
                   "hstu_rms_norm_bwd: workspace is null, not 16-byte aligned or too small");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(dy, eb) && norm_aligned(x, eb) && norm_aligned(dx, eb) && norm_aligned(weight, web) &&
                       norm_aligned(dweight, web),
                   "hstu_rms_norm_bwd: a base pointer is not aligned to the element size");

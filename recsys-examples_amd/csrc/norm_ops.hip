@@ -39,7 +39,7 @@ extern "C" int mi355_hstu_layer_norm_fwd(const void* x, int64_t x_stride, int64_
   MI355_CHECK_ARG(x_stride >= D && y_stride >= D, "hstu_layer_norm_fwd: a row stride is smaller than D");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(x && y && mean && rstd, "hstu_layer_norm_fwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(x, eb) && norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web),
                   "hstu_layer_norm_fwd: a base pointer is not aligned to the element size");
   NormVec nv{D % (16 / eb) == 0 ? 16 / eb : 1};
@@ -77,7 +77,7 @@ extern "C" int mi355_hstu_layer_norm_bwd(const void* dy, int64_t dy_stride, cons
                                  workspace_bytes >= mi355_hstu_layer_norm_bwd_workspace_bytes(rows, D)),
                   "hstu_layer_norm_bwd: workspace is null, not 16-byte aligned or too small");
   MI355_CHECK_ARG(rows == 0 || (dy && x && dx && mean && rstd), "hstu_layer_norm_bwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(dy, eb) && norm_aligned(x, eb) && norm_aligned(dx, eb) && norm_aligned(dx_accumulate, eb) &&
                       norm_aligned(weight, web) && norm_aligned(dweight, web) && norm_aligned(dbias, web),
                   "hstu_layer_norm_bwd: a base pointer is not aligned to the element size");
@@ -111,7 +111,7 @@ extern "C" int mi355_hstu_ln_mul_dropout_fwd(const void* x, int64_t x_stride, co
                   "hstu_ln_mul_dropout_fwd: a stride is smaller than the extent it steps over");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(x && u && y && weight && bias && mean && rstd, "hstu_ln_mul_dropout_fwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(x, eb) && norm_aligned(u, eb) && norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web),
                   "hstu_ln_mul_dropout_fwd: a base pointer is not aligned to the element size");
   MI355_CHECK_ARG((H - 1) * u_stride1 * eb < ((int64_t)1 << 31), "hstu_ln_mul_dropout_fwd: u head stride too large");
@@ -149,7 +149,7 @@ extern "C" int mi355_hstu_ln_mul_dropout_bwd(const void* dy, int64_t dy_stride, 
                   "hstu_ln_mul_dropout_bwd: workspace is null, not 16-byte aligned or too small");
   MI355_CHECK_ARG(rows == 0 || (dy && x && u && dx && du && weight && bias && mean && rstd),
                   "hstu_ln_mul_dropout_bwd: null buffer with rows > 0");
-  const int eb = norm_ebytes(dtype), web = norm_ebytes(weight_dtype);
+  const int eb = elem_bytes(dtype), web = elem_bytes(weight_dtype);
   MI355_CHECK_ARG(norm_aligned(dy, eb) && norm_aligned(x, eb) && norm_aligned(u, eb) && norm_aligned(dx, eb) && norm_aligned(du, eb) &&
                       norm_aligned(y, eb) && norm_aligned(weight, web) && norm_aligned(bias, web) && norm_aligned(dweight, web) &&
                       norm_aligned(dbias, web),

@@ -4,11 +4,11 @@
 // backward (:141-211), _add_timestamp_position_embeddings_kernel (:309-404) and the sort-and-atomics backward
 // _add_embeddings_bwd_kernel (:434-482).  Written for wave64 from the arithmetic; the reference is Triton.
 //
-// Forward (both ops): the row mover of jagged_ops.hip with arithmetic in the copy.  One wave per run of 2^k rows (k = 2 .. 6):
-//   resolve: lane l owns row m0 + l: binary search of the offsets for its sequence, the table row index (or the two of the
-//            timestamp form), the addresses of its input row, its output row and its table rows.
-//   stream:  the run is one flat stream of D / V pieces of V elements per row; lane i of a step takes piece i and gets its
-//            row's addresses from the owning lane with shuffles.  Loads are unconditional (an idle lane reads a zero word).
+// Forward (both ops): the row run of jagged_dev.h with arithmetic in the copy.  Their own:
+//   resolve: lane l's row -> its sequence (binary search of the offsets), the table row index (or the two of the timestamp
+//            form), the addresses of its input row, its output row and its table rows.
+//   stream:  wave_add_run, the load and store steps of jagged_dev.h's piece loop: a piece is V elements (Vec<>, vec_dev.h), up to
+//            three loads a step, the add and its one rounding in the store step.
 // V is the widest of 8 / 4 / 2 / 1 elements that divides D and that every base pointer and row stride of the call allows.
 //
 // Backward: a table-row gradient is a sum of d_out rows, bitwise reproducible, so no float atomics.  Two passes:
@@ -32,8 +32,6 @@
 
 namespace mi355 {
 
-static __device__ __attribute__((aligned(32))) uint32_t g_pos_zero[8];
-
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 struct PosArgs {                 // mi355_hstu_add_position_embeddings and the scaling of its backward
@@ -44,8 +42,7 @@ struct PosArgs {                 // mi355_hstu_add_position_embeddings and the s
   const int64_t* ind_off;        // [B] or null
   int64_t N, B, K;
   float scale;
-  uint32_t vpr;                  // pieces per row = D / V
-  int vpr_shift, rpw_log2;
+  RunPlan plan;                  // pieces of V elements
 };
 
 struct TsArgs {                  // mi355_hstu_add_timestamp_position_embeddings
@@ -60,8 +57,7 @@ struct TsArgs {                  // mi355_hstu_add_timestamp_position_embeddings
   int64_t N, B, Np, Nt, mcsl, ntb, time_delta;
   float incr, tscale;
   int interleave, fn;
-  uint32_t vpr;
-  int vpr_shift, rpw_log2;
+  RunPlan plan;
 };
 
 struct PosBwdArgs {              // the two passes of mi355_hstu_add_position_embeddings_bwd
@@ -90,54 +86,42 @@ __device__ __forceinline__ void wave_add_run(uintptr_t src, uintptr_t dst, uintp
                                              int vpr_shift, float scale) {
   constexpr int UN = 2;
   constexpr uintptr_t SB = Vec<DT, V>::BYTES, TB = Vec<TDT, V>::BYTES;
-  const uint32_t lane = (uint32_t)lane_id();
-  const uint32_t total = (uint32_t)nrows * vpr;
-  const uintptr_t zero = (uintptr_t)g_pos_zero;
-  for (uint32_t base = 0; base < total; base += 64 * UN) {
-    float x[UN][V], p[UN][V], q[UN][V];
-    uintptr_t d[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const uint32_t i = base + u * 64 + lane;
-      const bool in = i < total;
-      const uint32_t ic = in ? i : 0u;
-      const uint32_t row = vpr_shift >= 0 ? ic >> vpr_shift : ic / vpr;
-      const uintptr_t col = (uintptr_t)(ic - row * vpr);
-      const uintptr_t s = shfl_addr(src, (int)row), dd = shfl_addr(dst, (int)row), a0 = shfl_addr(t0, (int)row);
-      const bool ok = in && s != 0 && dd != 0;
-      Vec<DT, V>::ld(ok ? s + col * SB : zero, x[u]);
-      Vec<TDT, V>::ld(ok && a0 != 0 ? a0 + col * TB : zero, p[u]);
-      if constexpr (TS) {
-        const uintptr_t a1 = shfl_addr(t1, (int)row);
-        Vec<TDT, V>::ld(ok && a1 != 0 ? a1 + col * TB : zero, q[u]);
-      }
-      d[u] = ok ? dd + col * SB : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      if (d[u]) {
-        float o[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          if constexpr (TS) o[e] = x[u][e] + Elem<DT>::rnd(p[u][e] + q[u][e]);
-          else o[e] = __fmaf_rn(x[u][e], scale, p[u][e]);
+  const uintptr_t zero = (uintptr_t)g_zero_piece;
+  float x[UN][V], p[UN][V], q[UN][V];
+  uintptr_t d[UN];
+  wave_run_pieces<UN>(
+      nrows, vpr, vpr_shift,
+      [&](int u, bool in, int row, uint32_t piece) {
+        const uintptr_t col = (uintptr_t)piece;
+        const uintptr_t s = shfl_addr(src, row), dd = shfl_addr(dst, row), a0 = shfl_addr(t0, row);
+        const bool ok = in && s != 0 && dd != 0;
+        Vec<DT, V>::ld(ok ? s + col * SB : zero, x[u]);
+        Vec<TDT, V>::ld(ok && a0 != 0 ? a0 + col * TB : zero, p[u]);
+        if constexpr (TS) {
+          const uintptr_t a1 = shfl_addr(t1, row);
+          Vec<TDT, V>::ld(ok && a1 != 0 ? a1 + col * TB : zero, q[u]);
         }
-        Vec<DT, V>::st(d[u], o);
-      }
-    }
-  }
+        d[u] = ok ? dd + col * SB : 0;
+      },
+      [&](int u) {
+        if (d[u]) {
+          float o[V];
+#pragma unroll
+          for (int e = 0; e < V; ++e) {
+            if constexpr (TS) o[e] = x[u][e] + Elem<DT>::rnd(p[u][e] + q[u][e]);
+            else o[e] = __fmaf_rn(x[u][e], scale, p[u][e]);
+          }
+          Vec<DT, V>::st(d[u], o);
+        }
+      });
 }
 
 template <int DT, int TDT, int V>
 __global__ __launch_bounds__(256) void hstu_pos_add_kernel(const PosArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.N) return;   // (wave-uniform)
-  const int64_t left = a.N - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.N, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   const int64_t b = sample_of(a.offsets, a.B, m);
   const int64_t s = a.offsets[b], e = a.offsets[b + 1];
   const bool ok = have && m >= s && m < e;
@@ -147,19 +131,15 @@ __global__ __launch_bounds__(256) void hstu_pos_add_kernel(const PosArgs a) {
   const uintptr_t src = ok ? a.in + (uintptr_t)m * a.in_stride : 0;
   const uintptr_t dst = ok ? a.out + (uintptr_t)m * a.out_stride : 0;
   const uintptr_t tab = ok && a.dense ? a.dense + (uintptr_t)idx * a.dense_stride : 0;
-  wave_add_run<DT, TDT, V, false>(src, dst, tab, 0, nrows, a.vpr, a.vpr_shift, a.scale);
+  wave_add_run<DT, TDT, V, false>(src, dst, tab, 0, run.nrows, a.plan.vpr, a.plan.vpr_shift, a.scale);
 }
 
 template <int DT, int TDT, int V>
 __global__ __launch_bounds__(256) void hstu_ts_pos_add_kernel(const TsArgs a) {
-  const int lane = lane_id();
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t m0 = wave << a.rpw_log2;
-  if (m0 >= a.N) return;
-  const int64_t left = a.N - m0;
-  const int nrows = left < (1 << a.rpw_log2) ? (int)left : (1 << a.rpw_log2);
-  const bool have = lane < nrows;
-  const int64_t m = m0 + (have ? lane : 0);
+  RowRun run;
+  if (!row_run(a.N, a.plan.rpw_log2, run)) return;   // (wave-uniform)
+  const bool have = run.have;
+  const int64_t m = run.m;
   const int64_t b = sample_of(a.offsets, a.B, m);
   const int64_t s = a.offsets[b], e = a.offsets[b + 1];
   const bool ok = have && m >= s && m < e && e <= a.N;
@@ -188,14 +168,14 @@ __global__ __launch_bounds__(256) void hstu_ts_pos_add_kernel(const TsArgs a) {
   const uintptr_t dst = ok ? a.out + (uintptr_t)m * a.out_stride : 0;
   const uintptr_t t0 = ok ? a.pos + (uintptr_t)p * a.pos_stride : 0;
   const uintptr_t t1 = ok ? a.ts + (uintptr_t)t * a.ts_stride : 0;
-  wave_add_run<DT, TDT, V, true>(src, dst, t0, t1, nrows, a.vpr, a.vpr_shift, 1.f);
+  wave_add_run<DT, TDT, V, true>(src, dst, t0, t1, run.nrows, a.plan.vpr, a.plan.vpr_shift, 1.f);
 }
 
 // acc += rows [r0, r1) of the wave's chunk, piece c, in row order: lane r holds the address of row r (0: adds nothing)
 template <int DT, int V>
 __device__ __forceinline__ void wave_sum_rows(uintptr_t addr, int r0, int r1, uint32_t c, bool active, float (&acc)[V]) {
   constexpr int UN = 4;
-  const uintptr_t zero = (uintptr_t)g_pos_zero;
+  const uintptr_t zero = (uintptr_t)g_zero_piece;
   for (int r = r0; r < r1; r += UN) {
     float x[UN][V];
 #pragma unroll
@@ -216,7 +196,7 @@ template <int V>
 __device__ __forceinline__ void wave_sum_partials(uintptr_t partial, int64_t D, int64_t j0, int64_t j1, int64_t o, uint32_t c,
                                                   bool active, float (&acc)[V]) {
   constexpr int UN = 8;
-  const uintptr_t zero = (uintptr_t)g_pos_zero;
+  const uintptr_t zero = (uintptr_t)g_zero_piece;
   for (int64_t j = j0; j <= j1; j += UN) {
     float x[UN][V];
 #pragma unroll
@@ -273,7 +253,7 @@ __global__ __launch_bounds__(256) void hstu_pos_dense_grad_kernel(const PosBwdAr
   const int64_t k = w / a.nslab;
   const uint32_t c = (uint32_t)(w - k * a.nslab) * 64 + lane;
   const bool active = c < a.vpr;
-  const uintptr_t zero = (uintptr_t)g_pos_zero;
+  const uintptr_t zero = (uintptr_t)g_zero_piece;
   float acc[V] = {};
   // 64 sequences at a time, lane l resolving sequence b0 + l; then only the sequences that contribute are visited, in order
   for (int64_t b0 = 0; b0 < a.B; b0 += 64) {
@@ -378,8 +358,6 @@ __global__ __launch_bounds__(256) void hstu_index_sum_kernel(const IdxArgs a) {
   if (active) Vec<TDT, V>::st(a.out + (uintptr_t)k * a.out_stride + (uintptr_t)c * Vec<TDT, V>::BYTES, acc);
 }
 
-static inline int ebytes(int dtype) { return dtype == kF32 ? 4 : (dtype == kBF16 || dtype == kF16) ? 2 : 0; }
-
 // most elements per access (8 / 4 / 2 / 1) that a buffer of `eb`-byte elements allows: base pointer and row stride
 static inline int max_v(int v, const void* p, int64_t stride_bytes, int eb) {
   const uint64_t x = (uint64_t)(uintptr_t)p | (uint64_t)stride_bytes;
@@ -417,7 +395,7 @@ using namespace mi355;
 
 #define POS_CHECK_COMMON(NAME, rows, D, dtype, tdtype, batch)                                                        \
   MI355_CHECK_ARG(D > 0 && D <= (int64_t)(1 << 22), NAME ": D must be in 1 .. 2^22");                                 \
-  MI355_CHECK_ARG(ebytes(dtype) != 0, NAME ": unsupported dtype");                                                    \
+  MI355_CHECK_ARG(elem_bytes(dtype) != 0, NAME ": unsupported dtype");                                               \
   MI355_CHECK_ARG(tdtype == kF32 || tdtype == dtype, NAME ": a table is fp32 or has the dtype of the rows");         \
   MI355_CHECK_ARG(rows >= 0 && rows < ((int64_t)1 << 36), NAME ": rows must be in 0 .. 2^36");                        \
   MI355_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 31), NAME ": batch must be in 1 .. 2^31")
@@ -438,7 +416,7 @@ extern "C" int mi355_hstu_add_position_embeddings(const void* jagged, int64_t ja
                   "hstu_add_position_embeddings: a row stride is smaller than D");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(jagged && out, "hstu_add_position_embeddings: null buffer with rows > 0");
-  const int eb = ebytes(dtype), teb = ebytes(dense_dtype);
+  const int eb = elem_bytes(dtype), teb = elem_bytes(dense_dtype);
   MI355_CHECK_ARG(aligned_to(jagged, jagged_stride, eb) && aligned_to(out, out_stride, eb) && aligned_to(dense, dense_stride, teb),
                   "hstu_add_position_embeddings: a base pointer is not aligned to the element size");
   int v = max_v_of_d(D);
@@ -450,10 +428,8 @@ extern "C" int mi355_hstu_add_position_embeddings(const void* jagged, int64_t ja
   a.in_stride = jagged_stride * eb; a.out_stride = out_stride * eb; a.dense_stride = dense_stride * teb;
   a.offsets = offsets; a.high = high_inds; a.ind_off = ind_offsets;
   a.N = rows; a.B = batch; a.K = K; a.scale = scale;
-  a.vpr = (uint32_t)(D / v);
-  a.vpr_shift = log2_or_minus1(a.vpr);
-  a.rpw_log2 = rows_per_wave_log2(rows, (uint64_t)D * eb);
-  const unsigned grid = (unsigned)ceil_div(ceil_div(rows, (int64_t)1 << a.rpw_log2), 4);
+  unsigned grid;
+  if (const int rc = plan_run(rows, (uint64_t)D * eb, D / v, "hstu_add_position_embeddings", a.plan, grid)) return rc;
   POS_SWITCH_V(v, POS_SWITCH_DT_TDT(dtype, dense_dtype, hstu_pos_add_kernel<DT, TDT, V><<<dim3(grid), dim3(256), 0, stream>>>(a)));
   MI355_LAUNCH_CHECK();
   return MI355_OK;
@@ -478,7 +454,7 @@ extern "C" int mi355_hstu_add_position_embeddings_bwd(const void* d_out, int64_t
   MI355_CHECK_ARG(workspace && ((uintptr_t)workspace & 31) == 0 &&
                       workspace_bytes >= mi355_hstu_add_position_embeddings_bwd_workspace_bytes(rows, batch, D),
                   "hstu_add_position_embeddings_bwd: workspace is null, not 32-byte aligned or too small");
-  const int eb = ebytes(dtype), teb = ebytes(dense_dtype);
+  const int eb = elem_bytes(dtype), teb = elem_bytes(dense_dtype);
   MI355_CHECK_ARG(aligned_to(d_out, d_out_stride, eb) && aligned_to(d_jagged, d_jagged_stride, eb) &&
                       aligned_to(d_dense, d_dense_stride, teb),
                   "hstu_add_position_embeddings_bwd: a base pointer is not aligned to the element size");
@@ -491,10 +467,8 @@ extern "C" int mi355_hstu_add_position_embeddings_bwd(const void* d_out, int64_t
     s.in_stride = d_out_stride * eb; s.out_stride = d_jagged_stride * eb; s.dense_stride = 0;
     s.offsets = offsets; s.high = high_inds; s.ind_off = nullptr;
     s.N = rows; s.B = batch; s.K = K; s.scale = scale;
-    s.vpr = (uint32_t)(D / v);
-    s.vpr_shift = log2_or_minus1(s.vpr);
-    s.rpw_log2 = rows_per_wave_log2(rows, (uint64_t)D * eb);
-    const unsigned grid = (unsigned)ceil_div(ceil_div(rows, (int64_t)1 << s.rpw_log2), 4);
+    unsigned grid;
+    if (const int rc = plan_run(rows, (uint64_t)D * eb, D / v, "hstu_add_position_embeddings_bwd", s.plan, grid)) return rc;
     POS_SWITCH_V(v, POS_SWITCH_DT(dtype, DT, hstu_pos_add_kernel<DT, DT, V><<<dim3(grid), dim3(256), 0, stream>>>(s)));
     MI355_LAUNCH_CHECK();
   }
@@ -541,7 +515,7 @@ extern "C" int mi355_hstu_add_timestamp_position_embeddings(
                   "hstu_add_timestamp_position_embeddings: a row stride is smaller than D");
   if (rows == 0) return MI355_OK;
   MI355_CHECK_ARG(seq && out && timestamps, "hstu_add_timestamp_position_embeddings: null buffer with rows > 0");
-  const int eb = ebytes(dtype), teb = ebytes(table_dtype);
+  const int eb = elem_bytes(dtype), teb = elem_bytes(table_dtype);
   MI355_CHECK_ARG(aligned_to(seq, seq_stride, eb) && aligned_to(out, out_stride, eb) && aligned_to(pos_emb, pos_stride, teb) &&
                       aligned_to(ts_emb, ts_stride, teb),
                   "hstu_add_timestamp_position_embeddings: a base pointer is not aligned to the element size");
@@ -558,10 +532,8 @@ extern "C" int mi355_hstu_add_timestamp_position_embeddings(
   a.N = rows; a.B = batch; a.Np = Np; a.Nt = Nt; a.mcsl = max_contextual_seq_len; a.ntb = num_time_buckets;
   a.time_delta = time_delta; a.incr = time_bucket_increments; a.tscale = time_bucket_scale;
   a.interleave = interleave_targets != 0; a.fn = time_bucket_fn;
-  a.vpr = (uint32_t)(D / v);
-  a.vpr_shift = log2_or_minus1(a.vpr);
-  a.rpw_log2 = rows_per_wave_log2(rows, (uint64_t)D * eb);
-  const unsigned grid = (unsigned)ceil_div(ceil_div(rows, (int64_t)1 << a.rpw_log2), 4);
+  unsigned grid;
+  if (const int rc = plan_run(rows, (uint64_t)D * eb, D / v, "hstu_add_timestamp_position_embeddings", a.plan, grid)) return rc;
   POS_SWITCH_V(v, POS_SWITCH_DT_TDT(dtype, table_dtype, hstu_ts_pos_add_kernel<DT, TDT, V><<<dim3(grid), dim3(256), 0, stream>>>(a)));
   MI355_LAUNCH_CHECK();
   return MI355_OK;
@@ -587,7 +559,7 @@ extern "C" int mi355_hstu_index_rows_sum(const void* d_out, int64_t d_out_stride
   MI355_CHECK_ARG(workspace && ((uintptr_t)workspace & 31) == 0 &&
                       workspace_bytes >= mi355_hstu_index_rows_sum_workspace_bytes(count, K, D),
                   "hstu_index_rows_sum: workspace is null, not 32-byte aligned or too small");
-  const int eb = ebytes(dtype), teb = ebytes(table_dtype);
+  const int eb = elem_bytes(dtype), teb = elem_bytes(table_dtype);
   MI355_CHECK_ARG(aligned_to(d_out, d_out_stride, eb) && aligned_to(d_table, table_stride, teb),
                   "hstu_index_rows_sum: a base pointer is not aligned to the element size");
   int v = max_v_of_d(D);
