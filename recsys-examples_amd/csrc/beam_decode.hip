@@ -18,7 +18,7 @@
 //    softmax in fp32 on the vector ALU (online), then folds in the ns context partials by log-sum-exp and writes `out` in
 //    the dtype of q and `lse` in fp32.  An index outside [0, decode_nums W) is never dereferenced: that key is absent.
 #include "common.h"
-#include "softmax_tile_dev.h"
+#include "softmax_mask_dev.h"
 #include "../../include/recsys_amd.h"
 
 #include <math.h>
@@ -56,11 +56,7 @@ __global__ void __launch_bounds__(256) beam_ctx_kernel(BeamCtxArgs a) {
   int64_t row0 = 0;
   int len = a.Sk;
   if (a.cu) {
-    int64_t s = a.cu[b], e = a.cu[b + 1];
-    s = s < 0 ? 0 : (s > a.total_k ? a.total_k : s);
-    e = e < s ? s : (e > a.total_k ? a.total_k : e);
-    row0 = s;
-    len = (int)(e - s);
+    SM_SEQ_BOUNDS(a.cu, b, a.total_k, row0, len);
   } else if (a.seqused) {
     const int u = a.seqused[b];
     len = u < 0 ? 0 : (u < a.Sk ? u : a.Sk);

@@ -19,28 +19,21 @@
 // skip_tiles = 0, or dense D = 64 at S = 8192).  As it stands the kernel compiles to the instructions it had before the
 // header existed.  A change to one of these pieces in the header has to be made here as well.
 //
-// Masks.  Every query row has a prefix bound `pre` (keys j < pre are seen) and, for the arbitrary kind, bands [lo, up):
-//   none     pre = Lk
-//   causal   pre = clamp(i + 1 + Lk - Lq, 0, Lk)                              (bottom-right aligned)
-//   func     pre = clamp(F[0][i], 0, Lk), bands clamp(F[2p-1][i]) .. clamp(F[2p][i]), an interval with start >= end is empty
-// A wave reduces the extents of its 32 rows (largest and smallest prefix, hull of the bands); the four waves' extents are
-// exchanged through LDS once.  A key tile is loaded only if some wave's prefix or hull reaches it, a wave computes only the
-// tiles its own rows reach, and the per-element test runs only on tiles that are not inside the smallest prefix of the wave.
-// A tile that is skipped would have had P = 0 for every row and the running max unchanged, so skipping changes no bit of the
-// result (skip_tiles = 0 turns the skipping off: every tile is loaded, computed and tested).
+// Masks, row extents and tile skipping are those of softmax_mask_dev.h, the one statement of their semantics, shared with
+// the backward (softmax_attn_bwd.hip).  This kernel takes that layer's functions where they leave its instructions alone
+// and its statement macros (SM_SEQ_BOUNDS, SM_ROW_EXT, SM_EXT_REDUCE, SM_NEXT_TILE, SM_MASK_BITS, SM_STORE_ROW) where a call
+// did not -- by the rule above: as it stands the kernel still compiles to the instructions it had.  One piece, the wave
+// exchange, is WRITTEN OUT and marked "equal to sm_ext_exchange_sync; edit both" (profiles/softmax_mask_refactor.txt).
 //
 // A row with no visible key -- in a tile (m stays -inf: the exponent is taken against 0, so P = exp2(-inf) = 0 and no
 // inf - inf arises) or at all (l = 0: out = 0, lse = -inf).
 #include "common.h"
-#include "softmax_tile_dev.h"
+#include "softmax_mask_dev.h"
 #include "../../include/recsys_amd.h"
 
 #include <math.h>
 
 namespace mi355 {
-
-constexpr int kPfNone = 0, kPfCausal = 1, kPfFunc = 2;
-constexpr int kPfIntMax = 0x7fffffff;
 
 struct PrefillArgs {
   const uint16_t* q;
@@ -48,7 +41,7 @@ struct PrefillArgs {
   const uint16_t* v;
   const int32_t* cu_q;      // [B + 1] or null (dense)
   const int32_t* cu_k;
-  const int32_t* func;      // kPfFunc only
+  const int32_t* func;      // kSmMaskFunc only
   uint16_t* out;            // [B, Sq, Hq, D] / [total_q, Hq, D]
   float* lse;               // [B, Hq, Sq] / [Hq, total_q], natural log
   int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
@@ -57,11 +50,6 @@ struct PrefillArgs {
   int B, Sq, Sk, Hq, G, nqt, n_func, skip;
   float scale_log2;
 };
-
-struct PfExt { int pmax, pmin, lo, hi; };   // largest / smallest prefix of a group of rows, hull [lo, hi) of their bands (lo >= hi: none)
-
-__device__ __forceinline__ int pf_clamp(int64_t x, int hi) { return x < 0 ? 0 : (x > hi ? hi : (int)x); }
-__device__ __forceinline__ bool pf_hits(const PfExt& e, int n0, int n1) { return n0 < e.pmax || (e.lo < n1 && e.hi > n0); }
 
 template <int DT, int D, int MK>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
@@ -85,48 +73,25 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
 
   int64_t qrow0 = 0, krow0 = 0;
   int Lq = a.Sq, Lk = a.Sk;
-  if (a.cu_q) {   // jagged: bounds clamped into the tensors and made monotone, so that no row outside them is ever read
-    int64_t s = a.cu_q[b], e = a.cu_q[b + 1];
-    s = s < 0 ? 0 : (s > a.total_q ? a.total_q : s);
-    e = e < s ? s : (e > a.total_q ? a.total_q : e);
-    qrow0 = s; Lq = (int)(e - s);
-    s = a.cu_k[b]; e = a.cu_k[b + 1];
-    s = s < 0 ? 0 : (s > a.total_k ? a.total_k : s);
-    e = e < s ? s : (e > a.total_k ? a.total_k : e);
-    krow0 = s; Lk = (int)(e - s);
+  if (a.cu_q) {   // jagged
+    SM_SEQ_BOUNDS(a.cu_q, b, a.total_q, qrow0, Lq);
+    SM_SEQ_BOUNDS(a.cu_k, b, a.total_k, krow0, Lk);
   }
   if (qt * kSmRows >= Lq) return;   // (block-uniform: no barrier has been passed)
 
   const int i = qt * kSmRows + wv * 32 + r;   // query row of this lane inside its sequence
   const bool valid = i < Lq;
   const int32_t* frow = nullptr;
-  if constexpr (MK == kPfFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
+  if constexpr (MK == kSmMaskFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
 
   // ---- the row's extents, the wave's, the workgroup's
-  int pre = 0;
-  PfExt we{0, 0, kPfIntMax, 0};
-  if (valid) {
-    if constexpr (MK == kPfNone) pre = Lk;
-    if constexpr (MK == kPfCausal) pre = pf_clamp((int64_t)i + 1 + Lk - Lq, Lk);
-    if constexpr (MK == kPfFunc) {
-      pre = pf_clamp(frow[0], Lk);
-      for (int p = 1; p + 1 < a.n_func; p += 2) {
-        const int lo = pf_clamp(frow[(int64_t)p * a.f_sp], Lk), up = pf_clamp(frow[(int64_t)(p + 1) * a.f_sp], Lk);
-        if (lo < up) { we.lo = lo < we.lo ? lo : we.lo; we.hi = up > we.hi ? up : we.hi; }
-      }
-    }
-  }
-  we.pmax = pre; we.pmin = pre;   // (a row past the sequence end sees nothing: the wave then tests every tile it computes)
-#pragma unroll
-  for (int off = 1; off < 32; off <<= 1) {
-    const int x0 = __shfl_xor(we.pmax, off, 64), x1 = __shfl_xor(we.pmin, off, 64);
-    const int x2 = __shfl_xor(we.lo, off, 64), x3 = __shfl_xor(we.hi, off, 64);
-    we.pmax = x0 > we.pmax ? x0 : we.pmax; we.pmin = x1 < we.pmin ? x1 : we.pmin;
-    we.lo = x2 < we.lo ? x2 : we.lo; we.hi = x3 > we.hi ? x3 : we.hi;
-  }
+  int pre = 0; SmExt we{0, 0, kSmIntMax, 0};   // (a row past the sequence end sees nothing)
+  SM_ROW_EXT(MK, we, pre, valid, i, Lq, Lk, frow, a.f_sp, a.n_func);
+  SM_EXT_REDUCE(we, 32);
+  // (equal to sm_ext_exchange_sync; edit both)
   if (lane == 0) { sExt[4 * wv] = we.pmax; sExt[4 * wv + 1] = we.pmin; sExt[4 * wv + 2] = we.lo; sExt[4 * wv + 3] = we.hi; }
   __syncthreads();
-  PfExt be[4];
+  SmExt be[4];
 #pragma unroll
   for (int w = 0; w < 4; ++w) {
     be[w].pmax = __builtin_amdgcn_readfirstlane(sExt[4 * w]);
@@ -134,19 +99,10 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
     be[w].lo = __builtin_amdgcn_readfirstlane(sExt[4 * w + 2]);
     be[w].hi = __builtin_amdgcn_readfirstlane(sExt[4 * w + 3]);
   }
-  we.pmax = __builtin_amdgcn_readfirstlane(we.pmax); we.pmin = __builtin_amdgcn_readfirstlane(we.pmin);
-  we.lo = __builtin_amdgcn_readfirstlane(we.lo); we.hi = __builtin_amdgcn_readfirstlane(we.hi);
+  sm_ext_uniform(we);
 
   const int nt = (Lk + kSmKeys - 1) / kSmKeys;
-  // first tile at or after t that some wave reaches (nt: none)
-  auto next_tile = [&](int t) {
-    if (!skip) return t < nt ? t : nt;
-    for (; t < nt; ++t) {
-      const int n0 = t * kSmKeys, n1 = n0 + kSmKeys;
-      if (pf_hits(be[0], n0, n1) || pf_hits(be[1], n0, n1) || pf_hits(be[2], n0, n1) || pf_hits(be[3], n0, n1)) break;
-    }
-    return t;
-  };
+  auto next_tile = [&](int t) { SM_NEXT_TILE(skip, t, nt, be); return t; };
 
   sm_u32x4 qf[D / 16];
   {
@@ -215,29 +171,12 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
     const int tn = next_tile(t + 1);
     if (tn < nt) load_tile(tn);
 
-    if (!skip || pf_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
+    if (!skip || sm_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
       float p[32];
       T::scores(sK, qf, a.scale_log2, r, h, p);
       if (!skip || n1 > we.pmin) {   // some row of the wave does not see the whole tile through its prefix
         uint32_t ok = 0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-          const int key = n0 + sm_key_of(j, h);
-          ok |= (uint32_t)(key < pre) << j;
-        }
-        if constexpr (MK == kPfFunc) {
-          if (!skip || (we.lo < n1 && we.hi > n0)) {
-            for (int pp = 1; pp + 1 < a.n_func; pp += 2) {
-              int lo = 0, up = 0;
-              if (valid) { lo = pf_clamp(frow[(int64_t)pp * a.f_sp], Lk); up = pf_clamp(frow[(int64_t)(pp + 1) * a.f_sp], Lk); }
-#pragma unroll
-              for (int j = 0; j < 32; ++j) {
-                const int key = n0 + sm_key_of(j, h);
-                ok |= (uint32_t)((lo <= key) & (key < up)) << j;
-              }
-            }
-          }
-        }
+        SM_MASK_BITS(MK, ok, skip, we, n0, n1, h, valid, pre, Lk, frow, a.f_sp, a.n_func);
 #pragma unroll
         for (int j = 0; j < 32; ++j) p[j] = ((ok >> j) & 1u) ? p[j] : -INFINITY;
       }
@@ -282,15 +221,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
   if (valid) {
     const int64_t orow = (a.cu_q ? qrow0 : (int64_t)b * a.Sq) + i;
     uint16_t* op = a.out + (orow * a.Hq + hq) * D + 4 * h;
-#pragma unroll
-    for (int ii = 0; ii < D / 32; ++ii)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        sm_u32x2 x;
-        x[0] = M::pack2(o[ii][4 * g] * inv, o[ii][4 * g + 1] * inv);
-        x[1] = M::pack2(o[ii][4 * g + 2] * inv, o[ii][4 * g + 3] * inv);
-        *reinterpret_cast<sm_u32x2*>(op + 32 * ii + 8 * g) = x;
-      }
+    SM_STORE_ROW(M, D, op, o, inv);
     if (h == 0) {
       const int64_t li = a.cu_q ? (int64_t)hq * a.total_q + qrow0 + i : ((int64_t)b * a.Hq + hq) * a.Sq + i;
       a.lse[li] = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * kSmLn2 : -INFINITY;   // v_log_f32 is log2
@@ -301,9 +232,9 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillArgs a) {
 template <int DT, int D>
 static void pf_launch(int mask, dim3 grid, hipStream_t stream, const PrefillArgs& c) {
   const dim3 block(256);
-  if (mask == kPfNone) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfNone>), grid, block, 0, stream, c);
-  else if (mask == kPfCausal) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfCausal>), grid, block, 0, stream, c);
-  else hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kPfFunc>), grid, block, 0, stream, c);
+  if (mask == kSmMaskNone) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kSmMaskNone>), grid, block, 0, stream, c);
+  else if (mask == kSmMaskCausal) hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kSmMaskCausal>), grid, block, 0, stream, c);
+  else hipLaunchKernelGGL((prefill_attn_kernel<DT, D, kSmMaskFunc>), grid, block, 0, stream, c);
 }
 
 }  // namespace mi355
@@ -317,27 +248,7 @@ int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, in
                        int mask, const int32_t* func, int64_t n_func, int64_t func_heads, int64_t func_stride_b,
                        int64_t func_stride_h, int64_t func_stride_f, int64_t func_stride_s, float softmax_scale,
                        int skip_tiles, void* out, float* lse, int dtype, hipStream_t stream) {
-  MI355_CHECK_ARG(dtype == kBF16 || dtype == kF16, "prefill_attn: dtype must be bf16 or fp16");
-  MI355_CHECK_ARG(D == 64 || D == 128, "prefill_attn: head dim must be 64 or 128");
-  MI355_CHECK_ARG(B >= 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "prefill_attn: Hq must be a multiple of Hkv");
-  MI355_CHECK_ARG(Sq >= 0 && Sk >= 0 && total_q >= 0 && total_k >= 0, "prefill_attn: negative length");
-  MI355_CHECK_ARG(mask == kPfNone || mask == kPfCausal || mask == kPfFunc,
-                  "prefill_attn: mask must be 0 (none), 1 (causal) or 2 (arbitrary func)");
-  MI355_CHECK_ARG((cu_seqlens_q == nullptr) == (cu_seqlens_k == nullptr),
-                  "prefill_attn: cu_seqlens_q and cu_seqlens_k come together (jagged) or not at all (dense)");
-  const bool jagged = cu_seqlens_q != nullptr;
-  if (mask == kPfFunc) {
-    MI355_CHECK_ARG(!jagged, "prefill_attn: the arbitrary func mask applies to the dense form only (no cu_seqlens)");
-    MI355_CHECK_ARG(n_func >= 1 && n_func % 2 == 1, "prefill_attn: n_func must be odd and >= 1");
-    MI355_CHECK_ARG(func_heads == 1 || func_heads == Hq, "prefill_attn: func must have 1 or Hq heads");
-    MI355_CHECK_ARG(n_func <= INT32_MAX, "prefill_attn: n_func does not fit 31 bits");
-  } else {
-    MI355_CHECK_ARG(func == nullptr, "prefill_attn: func is given but the mask kind is not 2 (a causal or plain call takes none)");
-  }
-  MI355_CHECK_ARG(skip_tiles == 0 || skip_tiles == 1, "prefill_attn: skip_tiles must be 0 or 1");
-  MI355_CHECK_ARG(B <= INT32_MAX && Hq <= INT32_MAX && Sq <= INT32_MAX - kSmRows && Sk <= INT32_MAX - kSmKeys &&
-                      total_q <= INT32_MAX - kSmRows && total_k <= INT32_MAX - kSmKeys,
-                  "prefill_attn: a dimension does not fit 31 bits");
+  SM_ATTN_CHECK_COMMON("prefill_attn", kSmKeys, INT32_MAX, "n_func does not fit 31 bits");
   const int64_t rows = jagged ? total_q : B * Sq;
   if (B == 0 || rows == 0 || Sq == 0) return MI355_OK;
   MI355_CHECK_ARG(q && out && lse, "prefill_attn: null pointer");
@@ -348,22 +259,14 @@ int mi355_prefill_attn(const void* q, int64_t q_stride_b, int64_t q_stride_s, in
     MI355_CHECK_ARG(sm_aligned(k, k_stride_b, k_stride_s, k_stride_h) && sm_aligned(v, v_stride_b, v_stride_s, v_stride_h),
                     "prefill_attn: k / v rows need 16-byte alignment (base aligned, strides multiples of 8 elements)");
   }
-  if (mask == kPfFunc) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "prefill_attn: func is null or misaligned");
+  if (mask == kSmMaskFunc) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "prefill_attn: func is null or misaligned");
   const int64_t nqt = ceil_div(Sq, (int64_t)kSmRows);   // jagged: Sq is max_seqlen_q
   const int64_t nblocks = nqt * B * Hq;
   MI355_CHECK_ARG(nblocks <= INT32_MAX, "prefill_attn: launch too large");
 
   PrefillArgs c;
-  c.q = (const uint16_t*)q; c.k = (const uint16_t*)k; c.v = (const uint16_t*)v;
-  c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.func = func; c.out = (uint16_t*)out; c.lse = lse;
-  c.q_sb = jagged ? 0 : q_stride_b; c.q_ss = q_stride_s; c.q_sh = q_stride_h;
-  c.k_sb = jagged ? 0 : k_stride_b; c.k_ss = k_stride_s; c.k_sh = k_stride_h;
-  c.v_sb = jagged ? 0 : v_stride_b; c.v_ss = v_stride_s; c.v_sh = v_stride_h;
-  c.f_sb = func_stride_b; c.f_sh = func_heads == 1 ? 0 : func_stride_h; c.f_sp = func_stride_f; c.f_si = func_stride_s;
-  c.total_q = total_q; c.total_k = total_k;
-  c.B = (int)B; c.Sq = (int)Sq; c.Sk = (int)Sk; c.Hq = (int)Hq; c.G = (int)(Hq / Hkv); c.nqt = (int)nqt;
-  c.n_func = (int)n_func; c.skip = skip_tiles;
-  c.scale_log2 = softmax_scale * kSmLog2e;
+  SM_ATTN_FILL_COMMON(c);
+  c.out = (uint16_t*)out; c.lse = lse; c.nqt = (int)nqt;
   const dim3 grid((unsigned)nblocks);
   if (dtype == kBF16) {
     if (D == 64) pf_launch<kBF16, 64>(mask, grid, stream, c);

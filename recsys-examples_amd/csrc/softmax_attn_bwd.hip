@@ -12,8 +12,8 @@
 //   a wave 32 rows, the row on the lane; Q and dO fragments in registers.  Per key tile of 64: S^T = K Q^T and dP^T = V dO^T
 //   (SmTile::scores over the [key][D + 8] images of K and of V) come out in sm_key_of register order, and dS^T goes from the
 //   registers into dQ^T += K^T dS^T (SmTile::pv with the transposed K image in the place of V^T).  delta_i = sum_d dO_id out_id
-//   is taken in fp32 from the fragments (one __shfl_xor 32) and written for launch 2.  Key tiles are skipped exactly as
-//   prefill_attn_kernel skips them.
+//   is taken in fp32 from the fragments (one __shfl_xor 32) and written for launch 2.  Key tiles are skipped by the rule of
+//   prefill_attn_kernel: both expand SM_NEXT_TILE and call sm_hits of softmax_mask_dev.h, where the mask semantics are stated.
 // Launch 2, sm_bwd_dkdv_kernel: the mirror image.  A workgroup owns 128 keys of one kv head, a wave 32 keys, the key on the
 //   lane; K and V fragments in registers; the dK^T and dV^T accumulators stay live across the G query heads of the group (in
 //   head order: the GQA sum has a fixed order and stays inside the workgroup) and the query tiles of 64 rows.  Per tile Q and
@@ -36,15 +36,13 @@
 // inside the sequences is written, the caller zeroes nothing.  (Jagged: Sq / Sk are max_seqlen_q / max_seqlen_k and bound the
 // launches as Sq bounds the forward's; rows of a sequence at or past max_seqlen_q are treated as absent, as the forward does.)
 #include "common.h"
-#include "softmax_tile_dev.h"
+#include "softmax_mask_dev.h"
 #include "../../include/recsys_amd.h"
 
 #include <math.h>
 
 namespace mi355 {
 
-constexpr int kBwNone = 0, kBwCausal = 1, kBwFunc = 2;
-constexpr int kBwIntMax = 0x7fffffff;
 constexpr int kBwQRows = kSmKeys;      // query rows per tile of launch 2 (the tile that SmTile stages)
 constexpr int kBwKeys = 128;           // keys per workgroup of launch 2 (4 waves x 32)
 constexpr int kBwMaxFunc = 129;        // launch 2 stages n_func values per row in LDS
@@ -57,7 +55,7 @@ struct BwdArgs {
   const uint16_t* dout;
   const int32_t* cu_q;      // [B + 1] or null (dense)
   const int32_t* cu_k;
-  const int32_t* func;      // kBwFunc only
+  const int32_t* func;      // kSmMaskFunc only
   const float* lse;         // [B, Hq, Sq] / [Hq, total_q], natural log
   float* delta;             // same layout
   uint16_t* dq;             // [B, Sq, Hq, D] / [total_q, Hq, D]
@@ -70,11 +68,6 @@ struct BwdArgs {
   float scale_log2, scale;
 };
 
-struct BwExt { int pmax, pmin, lo, hi; };   // largest / smallest prefix of a group of rows, hull [lo, hi) of their bands (lo >= hi: none)
-
-__device__ __forceinline__ int bw_clamp(int64_t x, int hi) { return x < 0 ? 0 : (x > hi ? hi : (int)x); }
-__device__ __forceinline__ bool bw_hits(const BwExt& e, int n0, int n1) { return n0 < e.pmax || (e.lo < n1 && e.hi > n0); }
-
 template <int DT> __device__ __forceinline__ void bw_unpack(uint32_t u, float& lo, float& hi);
 template <> __device__ __forceinline__ void bw_unpack<kBF16>(uint32_t u, float& lo, float& hi) {
   lo = __uint_as_float(u << 16);
@@ -84,30 +77,6 @@ template <> __device__ __forceinline__ void bw_unpack<kF16>(uint32_t u, float& l
   const typename SmMma<kF16>::V2 x = __builtin_bit_cast(typename SmMma<kF16>::V2, u);
   lo = (float)x[0];
   hi = (float)x[1];
-}
-
-// sequence b of a jagged batch: bounds clamped into the tensors and made monotone, as in the forward
-__device__ __forceinline__ void bw_bounds(const int32_t* cu, int b, int64_t total, int64_t& row0, int& len) {
-  int64_t s = cu[b], e = cu[b + 1];
-  s = s < 0 ? 0 : (s > total ? total : s);
-  e = e < s ? s : (e > total ? total : e);
-  row0 = s;
-  len = (int)(e - s);
-}
-
-// fp32 accumulators (d in the registers, the row or key r on the lane) times c, rounded once, to row `dst` (element 4 h)
-template <int DT, int D>
-__device__ __forceinline__ void bw_store_row(uint16_t* dst, const sm_f32x16 (&o)[D / 32], float c) {
-  using M = SmMma<DT>;
-#pragma unroll
-  for (int ii = 0; ii < D / 32; ++ii)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      sm_u32x2 x;
-      x[0] = M::pack2(o[ii][4 * g] * c, o[ii][4 * g + 1] * c);
-      x[1] = M::pack2(o[ii][4 * g + 2] * c, o[ii][4 * g + 3] * c);
-      *reinterpret_cast<sm_u32x2*>(dst + 32 * ii + 8 * g) = x;
-    }
 }
 
 template <int DT, int D, int MK>
@@ -131,60 +100,26 @@ __global__ void __launch_bounds__(256) sm_bwd_dq_kernel(BwdArgs a) {
   int64_t qrow0 = 0, krow0 = 0;
   int Lq = a.Sq, Lk = a.Sk;
   if (a.cu_q) {
-    bw_bounds(a.cu_q, b, a.total_q, qrow0, Lq);
-    bw_bounds(a.cu_k, b, a.total_k, krow0, Lk);
+    sm_seq_bounds(a.cu_q, b, a.total_q, qrow0, Lq);
+    sm_seq_bounds(a.cu_k, b, a.total_k, krow0, Lk);
   }
   if (qt * kSmRows >= Lq) return;   // (block-uniform: no barrier has been passed)
 
   const int i = qt * kSmRows + wv * 32 + r;   // query row of this lane inside its sequence
   const bool valid = i < Lq;
   const int32_t* frow = nullptr;
-  if constexpr (MK == kBwFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
+  if constexpr (MK == kSmMaskFunc) frow = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh + (int64_t)i * a.f_si;
 
-  // ---- the row's extents, the wave's, the workgroup's (as prefill_attn_kernel)
-  int pre = 0;
-  BwExt we{0, 0, kBwIntMax, 0};
-  if (valid) {
-    if constexpr (MK == kBwNone) pre = Lk;
-    if constexpr (MK == kBwCausal) pre = bw_clamp((int64_t)i + 1 + Lk - Lq, Lk);
-    if constexpr (MK == kBwFunc) {
-      pre = bw_clamp(frow[0], Lk);
-      for (int p = 1; p + 1 < a.n_func; p += 2) {
-        const int lo = bw_clamp(frow[(int64_t)p * a.f_sp], Lk), up = bw_clamp(frow[(int64_t)(p + 1) * a.f_sp], Lk);
-        if (lo < up) { we.lo = lo < we.lo ? lo : we.lo; we.hi = up > we.hi ? up : we.hi; }
-      }
-    }
-  }
-  we.pmax = pre; we.pmin = pre;
-#pragma unroll
-  for (int off = 1; off < 32; off <<= 1) {
-    const int x0 = __shfl_xor(we.pmax, off, 64), x1 = __shfl_xor(we.pmin, off, 64);
-    const int x2 = __shfl_xor(we.lo, off, 64), x3 = __shfl_xor(we.hi, off, 64);
-    we.pmax = x0 > we.pmax ? x0 : we.pmax; we.pmin = x1 < we.pmin ? x1 : we.pmin;
-    we.lo = x2 < we.lo ? x2 : we.lo; we.hi = x3 > we.hi ? x3 : we.hi;
-  }
-  if (lane == 0) { sExt[4 * wv] = we.pmax; sExt[4 * wv + 1] = we.pmin; sExt[4 * wv + 2] = we.lo; sExt[4 * wv + 3] = we.hi; }
-  __syncthreads();
-  BwExt be[4];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    be[w].pmax = __builtin_amdgcn_readfirstlane(sExt[4 * w]);
-    be[w].pmin = __builtin_amdgcn_readfirstlane(sExt[4 * w + 1]);
-    be[w].lo = __builtin_amdgcn_readfirstlane(sExt[4 * w + 2]);
-    be[w].hi = __builtin_amdgcn_readfirstlane(sExt[4 * w + 3]);
-  }
-  we.pmax = __builtin_amdgcn_readfirstlane(we.pmax); we.pmin = __builtin_amdgcn_readfirstlane(we.pmin);
-  we.lo = __builtin_amdgcn_readfirstlane(we.lo); we.hi = __builtin_amdgcn_readfirstlane(we.hi);
+  // ---- the row's extents, the wave's, the workgroup's
+  int pre = 0; SmExt we{0, 0, kSmIntMax, 0};   // (a row past the sequence end sees nothing)
+  SM_ROW_EXT(MK, we, pre, valid, i, Lq, Lk, frow, a.f_sp, a.n_func);
+  sm_ext_reduce<32>(we);
+  SmExt be[4];
+  sm_ext_exchange_sync(sExt, wv, lane, we, be);
+  sm_ext_uniform(we);
 
   const int nt = (Lk + kSmKeys - 1) / kSmKeys;
-  auto next_tile = [&](int t) {   // first tile at or after t that some wave reaches (nt: none)
-    if (!skip) return t < nt ? t : nt;
-    for (; t < nt; ++t) {
-      const int n0 = t * kSmKeys, n1 = n0 + kSmKeys;
-      if (bw_hits(be[0], n0, n1) || bw_hits(be[1], n0, n1) || bw_hits(be[2], n0, n1) || bw_hits(be[3], n0, n1)) break;
-    }
-    return t;
-  };
+  auto next_tile = [&](int t) { SM_NEXT_TILE(skip, t, nt, be); return t; };
 
   // ---- the row's operands and constants: Q, dO, delta = dO . out (written for launch 2), the exponent offset lse log2 e
   const int64_t orow = (a.cu_q ? qrow0 : (int64_t)b * a.Sq) + i;
@@ -248,31 +183,14 @@ __global__ void __launch_bounds__(256) sm_bwd_dq_kernel(BwdArgs a) {
     const int tn = next_tile(t + 1);
     if (tn < nt) load_tile(tn);
 
-    if (!skip || bw_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
+    if (!skip || sm_hits(we, n0, n1)) {   // (wave-uniform; no barrier inside)
       float p[32], dp[32];
       T::scores(sK, qf, a.scale_log2, r, h, p);
       T::scores(sVr, dof, 1.0f, r, h, dp);
       uint32_t ok = 0xffffffffu;
       if (!skip || n1 > we.pmin) {   // some row of the wave does not see the whole tile through its prefix
         ok = 0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-          const int key = n0 + sm_key_of(j, h);
-          ok |= (uint32_t)(key < pre) << j;
-        }
-        if constexpr (MK == kBwFunc) {
-          if (!skip || (we.lo < n1 && we.hi > n0)) {
-            for (int pp = 1; pp + 1 < a.n_func; pp += 2) {
-              int lo = 0, up = 0;
-              if (valid) { lo = bw_clamp(frow[(int64_t)pp * a.f_sp], Lk); up = bw_clamp(frow[(int64_t)(pp + 1) * a.f_sp], Lk); }
-#pragma unroll
-              for (int j = 0; j < 32; ++j) {
-                const int key = n0 + sm_key_of(j, h);
-                ok |= (uint32_t)((lo <= key) & (key < up)) << j;
-              }
-            }
-          }
-        }
+        SM_MASK_BITS(MK, ok, skip, we, n0, n1, h, valid, pre, Lk, frow, a.f_sp, a.n_func);
       }
 #pragma unroll
       for (int j = 0; j < 32; ++j) {   // dS = P (dP - delta), in place of the score
@@ -284,7 +202,7 @@ __global__ void __launch_bounds__(256) sm_bwd_dq_kernel(BwdArgs a) {
     t = tn;
   }
 
-  if (valid) bw_store_row<DT, D>(a.dq + (orow * a.Hq + hq) * D + 4 * h, acc, a.scale);
+  if (valid) sm_store_row<DT, D>(a.dq + (orow * a.Hq + hq) * D + 4 * h, acc, a.scale);
 }
 
 template <int DT, int D, int MK>
@@ -310,8 +228,8 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
   int64_t qrow0 = 0, krow0 = 0;
   int Lq = a.Sq, Lk = a.Sk;
   if (a.cu_q) {
-    bw_bounds(a.cu_q, b, a.total_q, qrow0, Lq);
-    bw_bounds(a.cu_k, b, a.total_k, krow0, Lk);
+    sm_seq_bounds(a.cu_q, b, a.total_q, qrow0, Lq);
+    sm_seq_bounds(a.cu_k, b, a.total_k, krow0, Lk);
   }
   const int key0 = kt * kBwKeys;
   if (key0 >= Lk) return;   // (block-uniform: no barrier has been passed)
@@ -327,10 +245,10 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
   T::zero_acc(dk);
   T::zero_acc(dv);
 
-  const int nf = MK == kBwFunc ? a.n_func : 1;
+  const int nf = MK == kSmMaskFunc ? a.n_func : 1;
   const int nqt = (Lqv + kBwQRows - 1) / kBwQRows;
   int t0 = 0;
-  if (MK == kBwCausal && skip) {   // rows before key0 - (Lk - Lq) see none of this workgroup's keys
+  if (MK == kSmMaskCausal && skip) {   // rows before key0 - (Lk - Lq) see none of this workgroup's keys
     const int64_t first = (int64_t)key0 - ((int64_t)Lk - Lq);
     t0 = first > 0 ? (int)(first / kBwQRows) : 0;
   }
@@ -342,10 +260,10 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
     const uint16_t* dob = a.dout + (int64_t)b * a.do_sb + (int64_t)hq * a.do_sh + qrow0 * a.do_ss;
     const int64_t lbase = a.cu_q ? (int64_t)hq * a.total_q + qrow0 : ((int64_t)b * a.Hq + hq) * a.Sq;
     const int32_t* fb = nullptr;
-    if constexpr (MK == kBwFunc) fb = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh;
+    if constexpr (MK == kSmMaskFunc) fb = a.func + (int64_t)b * a.f_sb + (int64_t)hq * a.f_sh;
 
     for (int t = t0; t < nqt; ++t) {
-      if constexpr (MK == kBwFunc) {
+      if constexpr (MK == kSmMaskFunc) {
         if (skip) {
           // Scan ahead to the next tile that reaches this workgroup's keys, four tiles per step: wave w takes tile t + w, a
           // lane one of its rows straight from `func`, and one barrier publishes the four answers (slots alternate by step, so
@@ -353,23 +271,19 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
           // belong to other sequences; staging each of them to find that out cost two barriers and a round trip apiece.
           while (t < nqt) {
             const int tt = t + wv, i = tt * kBwQRows + lane;
-            BwExt x{0, 0, kBwIntMax, 0};
-            if (tt < nqt && i < Lqv) {
+            SmExt x{0, 0, kSmIntMax, 0};
+            if (tt < nqt && i < Lqv) {   // (equal to SM_ROW_EXT less pmin; edit both)
               const int32_t* fr = fb + (int64_t)i * a.f_si;
-              x.pmax = bw_clamp(fr[0], Lk);
+              x.pmax = sm_clamp(fr[0], Lk);
               for (int pp = 1; pp + 1 < nf; pp += 2) {
-                const int lo = bw_clamp(fr[(int64_t)pp * a.f_sp], Lk), up = bw_clamp(fr[(int64_t)(pp + 1) * a.f_sp], Lk);
-                if (lo < up) { x.lo = lo < x.lo ? lo : x.lo; x.hi = up > x.hi ? up : x.hi; }
+                const int lo = sm_clamp(fr[(int64_t)pp * a.f_sp], Lk), up = sm_clamp(fr[(int64_t)(pp + 1) * a.f_sp], Lk);
+                sm_ext_band(x, lo, up);
               }
             }
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-              const int x0 = __shfl_xor(x.pmax, off, 64), x2 = __shfl_xor(x.lo, off, 64), x3 = __shfl_xor(x.hi, off, 64);
-              x.pmax = x0 > x.pmax ? x0 : x.pmax; x.lo = x2 < x.lo ? x2 : x.lo; x.hi = x3 > x.hi ? x3 : x.hi;
-            }
+            sm_ext_reduce<64, false>(x);   // (pmin is not needed to find a tile)
             int* const slot = sHit + 4 * (scan & 1);
             ++scan;
-            if (lane == 0) slot[wv] = bw_hits(x, key0, key0 + kBwKeys) ? 1 : 0;   // (a tile past the end has no rows: no hit)
+            if (lane == 0) slot[wv] = sm_hits(x, key0, key0 + kBwKeys) ? 1 : 0;   // (a tile past the end has no rows: no hit)
             __syncthreads();
             const int first = slot[0] ? 0 : (slot[1] ? 1 : (slot[2] ? 2 : (slot[3] ? 3 : 4)));
             t += first;
@@ -379,10 +293,10 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
         }
       }
       const int q0 = t * kBwQRows;
-      if constexpr (MK != kBwFunc) {
+      if constexpr (MK != kSmMaskFunc) {
         if (skip) {   // the last row of the tile has its largest prefix: a tile that does not reach key0 is not loaded
           const int il = (q0 + kBwQRows < Lqv ? q0 + kBwQRows : Lqv) - 1;
-          const int pmax = MK == kBwNone ? Lk : bw_clamp((int64_t)il + 1 + Lk - Lq, Lk);
+          const int pmax = MK == kSmMaskNone ? Lk : sm_clamp((int64_t)il + 1 + Lk - Lq, Lk);
           if (pmax <= key0) continue;   // (block-uniform; no barrier has been passed in this step)
         }
       }
@@ -399,20 +313,20 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
           const float l = a.lse[lbase + i];
           if (l != -INFINITY) l2 = l * kSmLog2e;
           dl = a.delta[lbase + i];
-          if constexpr (MK == kBwNone) pre = Lk;
-          if constexpr (MK == kBwCausal) pre = bw_clamp((int64_t)i + 1 + Lk - Lq, Lk);
+          if constexpr (MK == kSmMaskNone) pre = Lk;
+          if constexpr (MK == kSmMaskCausal) pre = sm_clamp((int64_t)i + 1 + Lk - Lq, Lk);
         }
       }
       __syncthreads();   // the previous tile is no longer read
       if (tid < kBwQRows) {
         sL[tid] = l2;
         sDl[tid] = dl;
-        if constexpr (MK != kBwFunc) sF[tid] = pre;
+        if constexpr (MK != kSmMaskFunc) sF[tid] = pre;
       }
-      if constexpr (MK == kBwFunc) {
+      if constexpr (MK == kSmMaskFunc) {
         for (int idx = tid; idx < kBwQRows * nf; idx += 256) {
           const int row = idx & (kBwQRows - 1), p = idx >> 6, i = q0 + row;
-          sF[idx] = i < Lqv ? bw_clamp(fb[(int64_t)p * a.f_sp + (int64_t)i * a.f_si], Lk) : 0;
+          sF[idx] = i < Lqv ? sm_clamp(fb[(int64_t)p * a.f_sp + (int64_t)i * a.f_si], Lk) : 0;
         }
       }
       T::store_tile(sa, sQ, sdOt, tid);
@@ -420,23 +334,16 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
       __syncthreads();
 
       // the extents of the tile's 64 rows, for the wave's own decisions (every wave reduces the same staged values)
-      BwExt e{sF[lane], 0, kBwIntMax, 0};
+      SmExt e{sF[lane], 0, kSmIntMax, 0};
       e.pmin = e.pmax;
       for (int pp = 1; pp + 1 < nf; pp += 2) {
         const int lo = sF[pp * kBwQRows + lane], up = sF[(pp + 1) * kBwQRows + lane];
-        if (lo < up) { e.lo = lo < e.lo ? lo : e.lo; e.hi = up > e.hi ? up : e.hi; }
+        sm_ext_band(e, lo, up);
       }
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int x0 = __shfl_xor(e.pmax, off, 64), x1 = __shfl_xor(e.pmin, off, 64);
-        const int x2 = __shfl_xor(e.lo, off, 64), x3 = __shfl_xor(e.hi, off, 64);
-        e.pmax = x0 > e.pmax ? x0 : e.pmax; e.pmin = x1 < e.pmin ? x1 : e.pmin;
-        e.lo = x2 < e.lo ? x2 : e.lo; e.hi = x3 > e.hi ? x3 : e.hi;
-      }
-      e.pmax = __builtin_amdgcn_readfirstlane(e.pmax); e.pmin = __builtin_amdgcn_readfirstlane(e.pmin);
-      e.lo = __builtin_amdgcn_readfirstlane(e.lo); e.hi = __builtin_amdgcn_readfirstlane(e.hi);
+      SM_EXT_REDUCE(e, 64);
+      sm_ext_uniform(e);
 
-      if (!skip || bw_hits(e, kw0, kw0 + 32)) {   // (wave-uniform; no barrier inside)
+      if (!skip || sm_hits(e, kw0, kw0 + 32)) {   // (wave-uniform; no barrier inside)
         float p[32], dp[32];
         T::scores(sQ, kf, a.scale_log2, r, h, p);     // register j: query row sm_key_of(j, h) of the tile
         T::scores(sdO, vf, 1.0f, r, h, dp);
@@ -445,7 +352,7 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
           ok = 0;
 #pragma unroll
           for (int j = 0; j < 32; ++j) ok |= (uint32_t)(key < sF[sm_key_of(j, h)]) << j;
-          if constexpr (MK == kBwFunc) {
+          if constexpr (MK == kSmMaskFunc) {
             if (!skip || (e.lo < kw0 + 32 && e.hi > kw0)) {
               for (int pp = 1; pp + 1 < nf; pp += 2) {
                 const int* flo = sF + pp * kBwQRows;
@@ -478,8 +385,8 @@ __global__ void __launch_bounds__(256) sm_bwd_dkdv_kernel(BwdArgs a) {
 
   if (kvalid) {
     const int64_t krow = (a.cu_q ? krow0 : (int64_t)b * a.Sk) + key;
-    bw_store_row<DT, D>(a.dk + (krow * a.Hkv + hk) * D + 4 * h, dk, a.scale);
-    bw_store_row<DT, D>(a.dv + (krow * a.Hkv + hk) * D + 4 * h, dv, 1.0f);
+    sm_store_row<DT, D>(a.dk + (krow * a.Hkv + hk) * D + 4 * h, dk, a.scale);
+    sm_store_row<DT, D>(a.dv + (krow * a.Hkv + hk) * D + 4 * h, dv, 1.0f);
   }
 }
 
@@ -505,15 +412,15 @@ static int bw_launch_lds(dim3 grid, size_t smem, hipStream_t stream, const BwdAr
 template <int DT, int D, int MK>
 static int bw_launch_mask(dim3 gq, dim3 gk, hipStream_t stream, const BwdArgs& c) {
   if (gq.x > 0) hipLaunchKernelGGL((sm_bwd_dq_kernel<DT, D, MK>), gq, dim3(256), 0, stream, c);
-  if (gk.x > 0) return bw_launch_lds<sm_bwd_dkdv_kernel<DT, D, MK>>(gk, bw_dkdv_lds<DT, D>(MK == kBwFunc ? c.n_func : 1), stream, c);
+  if (gk.x > 0) return bw_launch_lds<sm_bwd_dkdv_kernel<DT, D, MK>>(gk, bw_dkdv_lds<DT, D>(MK == kSmMaskFunc ? c.n_func : 1), stream, c);
   return MI355_OK;
 }
 
 template <int DT, int D>
 static int bw_launch(int mask, dim3 gq, dim3 gk, hipStream_t stream, const BwdArgs& c) {
-  if (mask == kBwNone) return bw_launch_mask<DT, D, kBwNone>(gq, gk, stream, c);
-  if (mask == kBwCausal) return bw_launch_mask<DT, D, kBwCausal>(gq, gk, stream, c);
-  return bw_launch_mask<DT, D, kBwFunc>(gq, gk, stream, c);
+  if (mask == kSmMaskNone) return bw_launch_mask<DT, D, kSmMaskNone>(gq, gk, stream, c);
+  if (mask == kSmMaskCausal) return bw_launch_mask<DT, D, kSmMaskCausal>(gq, gk, stream, c);
+  return bw_launch_mask<DT, D, kSmMaskFunc>(gq, gk, stream, c);
 }
 
 }  // namespace mi355
@@ -529,27 +436,7 @@ int mi355_softmax_attn_bwd(const void* q, int64_t q_stride_b, int64_t q_stride_s
                            int skip_tiles, const void* out, const void* dout, int64_t dout_stride_b, int64_t dout_stride_s,
                            int64_t dout_stride_h, const float* lse, float* delta, void* dq, void* dk, void* dv, int dtype,
                            hipStream_t stream) {
-  MI355_CHECK_ARG(dtype == kBF16 || dtype == kF16, "softmax_attn_bwd: dtype must be bf16 or fp16");
-  MI355_CHECK_ARG(D == 64 || D == 128, "softmax_attn_bwd: head dim must be 64 or 128");
-  MI355_CHECK_ARG(B >= 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "softmax_attn_bwd: Hq must be a multiple of Hkv");
-  MI355_CHECK_ARG(Sq >= 0 && Sk >= 0 && total_q >= 0 && total_k >= 0, "softmax_attn_bwd: negative length");
-  MI355_CHECK_ARG(mask == kBwNone || mask == kBwCausal || mask == kBwFunc,
-                  "softmax_attn_bwd: mask must be 0 (none), 1 (causal) or 2 (arbitrary func)");
-  MI355_CHECK_ARG((cu_seqlens_q == nullptr) == (cu_seqlens_k == nullptr),
-                  "softmax_attn_bwd: cu_seqlens_q and cu_seqlens_k come together (jagged) or not at all (dense)");
-  const bool jagged = cu_seqlens_q != nullptr;
-  if (mask == kBwFunc) {
-    MI355_CHECK_ARG(!jagged, "softmax_attn_bwd: the arbitrary func mask applies to the dense form only (no cu_seqlens)");
-    MI355_CHECK_ARG(n_func >= 1 && n_func % 2 == 1, "softmax_attn_bwd: n_func must be odd and >= 1");
-    MI355_CHECK_ARG(func_heads == 1 || func_heads == Hq, "softmax_attn_bwd: func must have 1 or Hq heads");
-    MI355_CHECK_ARG(n_func <= kBwMaxFunc, "softmax_attn_bwd: n_func above 129 (64 bands) is not supported by the dK/dV pass");
-  } else {
-    MI355_CHECK_ARG(func == nullptr, "softmax_attn_bwd: func is given but the mask kind is not 2 (a causal or plain call takes none)");
-  }
-  MI355_CHECK_ARG(skip_tiles == 0 || skip_tiles == 1, "softmax_attn_bwd: skip_tiles must be 0 or 1");
-  MI355_CHECK_ARG(B <= INT32_MAX && Hq <= INT32_MAX && Sq <= INT32_MAX - kSmRows && Sk <= INT32_MAX - kBwKeys &&
-                      total_q <= INT32_MAX - kSmRows && total_k <= INT32_MAX - kBwKeys,
-                  "softmax_attn_bwd: a dimension does not fit 31 bits");
+  SM_ATTN_CHECK_COMMON("softmax_attn_bwd", kBwKeys, kBwMaxFunc, "n_func above 129 (64 bands) is not supported by the dK/dV pass");
   const int64_t qrows = jagged ? total_q : B * Sq, krows = jagged ? total_k : B * Sk;
   const bool has_q = B > 0 && qrows > 0 && Sq > 0, has_k = B > 0 && krows > 0 && Sk > 0;
   if (!has_q && !has_k) return MI355_OK;
@@ -567,25 +454,17 @@ int mi355_softmax_attn_bwd(const void* q, int64_t q_stride_b, int64_t q_stride_s
                         (uintptr_t)dk % 16 == 0 && (uintptr_t)dv % 16 == 0,
                     "softmax_attn_bwd: k / v / dk / dv rows need 16-byte alignment (base aligned, strides multiples of 8 elements)");
   }
-  if (mask == kBwFunc && has_q) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "softmax_attn_bwd: func is null or misaligned");
+  if (mask == kSmMaskFunc && has_q) MI355_CHECK_ARG(func && (uintptr_t)func % 4 == 0, "softmax_attn_bwd: func is null or misaligned");
   const int64_t nqt = has_q ? ceil_div(Sq, (int64_t)kSmRows) : 0;   // jagged: Sq / Sk are max_seqlen_q / max_seqlen_k
   const int64_t nkt = has_k ? ceil_div(Sk, (int64_t)kBwKeys) : 0;
   MI355_CHECK_ARG(nqt * B * Hq <= INT32_MAX && nkt * B * Hkv <= INT32_MAX, "softmax_attn_bwd: launch too large");
 
   BwdArgs c;
-  c.q = (const uint16_t*)q; c.k = (const uint16_t*)k; c.v = (const uint16_t*)v;
-  c.out = (const uint16_t*)out; c.dout = (const uint16_t*)dout;
-  c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.func = func; c.lse = lse; c.delta = delta;
+  SM_ATTN_FILL_COMMON(c);
+  c.out = (const uint16_t*)out; c.dout = (const uint16_t*)dout; c.lse = lse; c.delta = delta;
   c.dq = (uint16_t*)dq; c.dk = (uint16_t*)dk; c.dv = (uint16_t*)dv;
-  c.q_sb = jagged ? 0 : q_stride_b; c.q_ss = q_stride_s; c.q_sh = q_stride_h;
-  c.k_sb = jagged ? 0 : k_stride_b; c.k_ss = k_stride_s; c.k_sh = k_stride_h;
-  c.v_sb = jagged ? 0 : v_stride_b; c.v_ss = v_stride_s; c.v_sh = v_stride_h;
   c.do_sb = jagged ? 0 : dout_stride_b; c.do_ss = dout_stride_s; c.do_sh = dout_stride_h;
-  c.f_sb = func_stride_b; c.f_sh = func_heads == 1 ? 0 : func_stride_h; c.f_sp = func_stride_f; c.f_si = func_stride_s;
-  c.total_q = total_q; c.total_k = total_k;
-  c.B = (int)B; c.Sq = (int)Sq; c.Sk = (int)Sk; c.Hq = (int)Hq; c.Hkv = (int)Hkv; c.G = (int)(Hq / Hkv);
-  c.nqt = (int)nqt; c.nkt = (int)nkt; c.n_func = (int)n_func; c.skip = skip_tiles;
-  c.scale_log2 = softmax_scale * kSmLog2e; c.scale = softmax_scale;
+  c.Hkv = (int)Hkv; c.nqt = (int)nqt; c.nkt = (int)nkt; c.scale = softmax_scale;
   const dim3 gq((unsigned)(nqt * B * Hq)), gk((unsigned)(nkt * B * Hkv));
   int rc;
   if (dtype == kBF16) rc = D == 64 ? bw_launch<kBF16, 64>(mask, gq, gk, stream, c) : bw_launch<kBF16, 128>(mask, gq, gk, stream, c);

@@ -84,6 +84,62 @@ def _require_gpu(**tensors):
             raise PrefillAttnError(f"{name} must be a GPU tensor (there is no CPU path), got device {t.device}")
 
 
+def _validate_dense(q, k, v, causal, arbitrary, aux_tensors, unsupported, max_n_func=None):
+    """The checks of flash_attn_func, here and in softmax_attn.py: returns (mask, func).  max_n_func: the backward's limit."""
+    _refuse_unsupported(unsupported)
+    _validate_qkv(q, k, v, jagged=False)
+    func = None
+    mask = MASK_CAUSAL if causal else MASK_NONE
+    if arbitrary:
+        if causal:
+            _bad("arbitrary=True with causal=True: put the causal bound into the arbitrary_func instead")
+        if aux_tensors is None or len(aux_tensors) != 1:
+            _bad(f"arbitrary=True needs exactly one aux tensor (the arbitrary_func), got "
+                 f"{'None' if aux_tensors is None else len(aux_tensors)}")
+        func = aux_tensors[0]
+        if not isinstance(func, torch.Tensor) or func.dtype != torch.int32 or func.dim() != 4:
+            _bad("arbitrary_func must be an int32 tensor [B, 1 or Hq, n_func, >= Sq], got "
+                 f"{getattr(func, 'dtype', type(func).__name__)} {tuple(getattr(func, 'shape', ()))}")
+        B, Sq, Hq = q.shape[0], q.shape[1], q.shape[2]
+        if func.shape[0] != B or func.shape[1] not in (1, Hq) or func.shape[2] % 2 != 1 or func.shape[3] < Sq:
+            _bad(f"arbitrary_func must be [B={B}, 1 or Hq={Hq}, n_func (odd), >= Sq={Sq}], got shape {tuple(func.shape)}")
+        if max_n_func is not None and func.shape[2] > max_n_func:   # refused before the forward, not at backward time
+            _bad(f"arbitrary_func with n_func={func.shape[2]} > {max_n_func} is not supported by the backward")
+        mask = MASK_FUNC
+    elif aux_tensors:
+        _bad("aux_tensors are given but arbitrary=False")
+    _require_gpu(q=q, k=k, v=v, arbitrary_func=func)
+    return mask, func
+
+
+def _validate_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, unsupported):
+    """The checks of flash_attn_varlen_func, here and in softmax_attn.py: returns the contiguous (cu_seqlens_q, cu_seqlens_k)."""
+    _refuse_unsupported(unsupported)
+    _validate_qkv(q, k, v, jagged=True)
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.dtype != torch.int32 or cu.shape[0] < 1:
+            _bad(f"{name} must be an int32 tensor [B + 1], got {getattr(cu, 'dtype', type(cu).__name__)} "
+                 f"{tuple(getattr(cu, 'shape', ()))}")
+    if cu_seqlens_q.shape != cu_seqlens_k.shape:
+        _bad(f"cu_seqlens_q {tuple(cu_seqlens_q.shape)} and cu_seqlens_k {tuple(cu_seqlens_k.shape)} differ in length")
+    if not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or not isinstance(max_seqlen_k, int) or max_seqlen_k < 0:
+        _bad(f"max_seqlen_q / max_seqlen_k must be non-negative ints, got {max_seqlen_q!r}, {max_seqlen_k!r}")
+    _require_gpu(q=q, k=k, v=v, cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k)
+    return cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
+
+
+def _strides(jagged, *tensors):
+    """(batch, row, head) strides of each tensor as the C ABI takes them; a jagged tensor has no batch stride"""
+    return [(0, t.stride(0), t.stride(1)) if jagged else t.stride()[:3] for t in tensors]
+
+
+def _func_args(func):
+    """func, n_func, func_heads and the four func strides of the C ABI"""
+    if func is None:
+        return (N.ptr(None), 0, 0, 0, 0, 0, 0)
+    return (N.ptr(func), func.shape[2], func.shape[1], *func.stride())
+
+
 def _forward(q, k, v, cu_q, cu_k, max_q, mask, func, scale, skip_tiles):
     jagged = cu_q is not None
     q, k, v = _rows_aligned(q), _rows_aligned(k), _rows_aligned(v)
@@ -93,19 +149,14 @@ def _forward(q, k, v, cu_q, cu_k, max_q, mask, func, scale, skip_tiles):
         B, Sq, Sk, total_q, total_k = cu_q.shape[0] - 1, int(max_q), 0, q.shape[0], k.shape[0]
         out = torch.empty(total_q, Hq, D, device=dev, dtype=q.dtype)
         lse = torch.empty(Hq, total_q, device=dev, dtype=torch.float32)
-        qs, ks, vs = (0, q.stride(0), q.stride(1)), (0, k.stride(0), k.stride(1)), (0, v.stride(0), v.stride(1))
     else:
         B, Sq, Sk, total_q, total_k = q.shape[0], q.shape[1], k.shape[1], 0, 0
         out = torch.empty(B, Sq, Hq, D, device=dev, dtype=q.dtype)
         lse = torch.empty(B, Hq, Sq, device=dev, dtype=torch.float32)
-        qs, ks, vs = q.stride()[:3], k.stride()[:3], v.stride()[:3]
-    if func is not None:
-        fa = (N.ptr(func), func.shape[2], func.shape[1], *func.stride())
-    else:
-        fa = (N.ptr(None), 0, 0, 0, 0, 0, 0)
+    qs, ks, vs = _strides(jagged, q, k, v)
     N.check(N.lib().mi355_prefill_attn(
         N.ptr(q), *qs, N.ptr(k), *ks, N.ptr(v), *vs, N.ptr(cu_q), N.ptr(cu_k),
-        B, Sq, Sk, total_q, total_k, Hq, Hkv, D, mask, *fa, float(scale), int(skip_tiles),
+        B, Sq, Sk, total_q, total_k, Hq, Hkv, D, mask, *_func_args(func), float(scale), int(skip_tiles),
         N.ptr(out), N.ptr(lse), N.dt(q), N.stream()), "mi355_prefill_attn")
     return out, lse
 
@@ -134,27 +185,7 @@ def flash_attn_func(q, k, v, softmax_scale: Optional[float] = None, causal: bool
     """Dense softmax attention.  q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] -> out [B, Sq, Hq, D] (and lse [B, Hq, Sq] fp32
     with return_lse).  causal is aligned bottom-right.  arbitrary=True takes aux_tensors=[arbitrary_func].  The two
     linear_*_block_sparse_tensors are accepted and not read: the kernel derives its own tile skipping from the function."""
-    _refuse_unsupported(unsupported)
-    _validate_qkv(q, k, v, jagged=False)
-    func = None
-    mask = MASK_CAUSAL if causal else MASK_NONE
-    if arbitrary:
-        if causal:
-            _bad("arbitrary=True with causal=True: put the causal bound into the arbitrary_func instead")
-        if aux_tensors is None or len(aux_tensors) != 1:
-            _bad(f"arbitrary=True needs exactly one aux tensor (the arbitrary_func), got "
-                 f"{'None' if aux_tensors is None else len(aux_tensors)}")
-        func = aux_tensors[0]
-        if not isinstance(func, torch.Tensor) or func.dtype != torch.int32 or func.dim() != 4:
-            _bad("arbitrary_func must be an int32 tensor [B, 1 or Hq, n_func, >= Sq], got "
-                 f"{getattr(func, 'dtype', type(func).__name__)} {tuple(getattr(func, 'shape', ()))}")
-        B, Sq, Hq = q.shape[0], q.shape[1], q.shape[2]
-        if func.shape[0] != B or func.shape[1] not in (1, Hq) or func.shape[2] % 2 != 1 or func.shape[3] < Sq:
-            _bad(f"arbitrary_func must be [B={B}, 1 or Hq={Hq}, n_func (odd), >= Sq={Sq}], got shape {tuple(func.shape)}")
-        mask = MASK_FUNC
-    elif aux_tensors:
-        _bad("aux_tensors are given but arbitrary=False")
-    _require_gpu(q=q, k=k, v=v, arbitrary_func=func)
+    mask, func = _validate_dense(q, k, v, causal, arbitrary, aux_tensors, unsupported)
     out, lse = PrefillAttn.apply(q, k, v, None, None, 0, mask, func, _scale(softmax_scale, q.shape[-1]), skip_tiles)
     return (out, lse) if return_lse else out
 
@@ -166,18 +197,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     [B + 1] -> out [total_q, Hq, D] (and lse [Hq, total_q] fp32 with return_lse).  causal holds inside each sequence,
     aligned bottom-right.  max_seqlen_q bounds the launch: rows of a sequence at or past it are not computed.
     max_seqlen_k is not needed."""
-    _refuse_unsupported(unsupported)
-    _validate_qkv(q, k, v, jagged=True)
-    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
-        if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.dtype != torch.int32 or cu.shape[0] < 1:
-            _bad(f"{name} must be an int32 tensor [B + 1], got {getattr(cu, 'dtype', type(cu).__name__)} "
-                 f"{tuple(getattr(cu, 'shape', ()))}")
-    if cu_seqlens_q.shape != cu_seqlens_k.shape:
-        _bad(f"cu_seqlens_q {tuple(cu_seqlens_q.shape)} and cu_seqlens_k {tuple(cu_seqlens_k.shape)} differ in length")
-    if not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or not isinstance(max_seqlen_k, int) or max_seqlen_k < 0:
-        _bad(f"max_seqlen_q / max_seqlen_k must be non-negative ints, got {max_seqlen_q!r}, {max_seqlen_k!r}")
-    _require_gpu(q=q, k=k, v=v, cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k)
-    out, lse = PrefillAttn.apply(q, k, v, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), max_seqlen_q,
+    cu_q, cu_k = _validate_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, unsupported)
+    out, lse = PrefillAttn.apply(q, k, v, cu_q, cu_k, max_seqlen_q,
                                  MASK_CAUSAL if causal else MASK_NONE, None, _scale(softmax_scale, q.shape[-1]), skip_tiles)
     return (out, lse) if return_lse else out
 

@@ -49,18 +49,12 @@ def _backward(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, mask, func, sca
     delta = torch.empty_like(lse)
     if jagged:
         B, Sq, Sk, total_q, total_k = cu_q.shape[0] - 1, int(max_q), int(max_k), q.shape[0], k.shape[0]
-        qs, ks, vs = (0, q.stride(0), q.stride(1)), (0, k.stride(0), k.stride(1)), (0, v.stride(0), v.stride(1))
-        ds = (0, dout.stride(0), dout.stride(1))
     else:
         B, Sq, Sk, total_q, total_k = q.shape[0], q.shape[1], k.shape[1], 0, 0
-        qs, ks, vs, ds = q.stride()[:3], k.stride()[:3], v.stride()[:3], dout.stride()[:3]
-    if func is not None:
-        fa = (N.ptr(func), func.shape[2], func.shape[1], *func.stride())
-    else:
-        fa = (N.ptr(None), 0, 0, 0, 0, 0, 0)
+    qs, ks, vs, ds = _P._strides(jagged, q, k, v, dout)
     N.check(N.lib().mi355_softmax_attn_bwd(
         N.ptr(q), *qs, N.ptr(k), *ks, N.ptr(v), *vs, N.ptr(cu_q), N.ptr(cu_k),
-        B, Sq, Sk, total_q, total_k, Hq, Hkv, D, mask, *fa, float(scale), int(skip_tiles),
+        B, Sq, Sk, total_q, total_k, Hq, Hkv, D, mask, *_P._func_args(func), float(scale), int(skip_tiles),
         N.ptr(out), N.ptr(dout), *ds, N.ptr(lse), N.ptr(delta), N.ptr(dq), N.ptr(dk), N.ptr(dv), N.dt(q), N.stream()),
         "mi355_softmax_attn_bwd")
     return dq, dk, dv
@@ -93,29 +87,7 @@ def flash_attn_func(q, k, v, softmax_scale: Optional[float] = None, causal: bool
     (and lse [B, Hq, Sq] fp32 with return_lse; lse carries no gradient).  causal is aligned bottom-right.  arbitrary=True
     takes aux_tensors=[arbitrary_func].  The two linear_*_block_sparse_tensors are accepted and not read: the kernels derive
     their own tile skipping, forward and backward, from the function."""
-    _P._refuse_unsupported(unsupported)
-    _P._validate_qkv(q, k, v, jagged=False)
-    func = None
-    mask = MASK_CAUSAL if causal else MASK_NONE
-    if arbitrary:
-        if causal:
-            _P._bad("arbitrary=True with causal=True: put the causal bound into the arbitrary_func instead")
-        if aux_tensors is None or len(aux_tensors) != 1:
-            _P._bad(f"arbitrary=True needs exactly one aux tensor (the arbitrary_func), got "
-                    f"{'None' if aux_tensors is None else len(aux_tensors)}")
-        func = aux_tensors[0]
-        if not isinstance(func, torch.Tensor) or func.dtype != torch.int32 or func.dim() != 4:
-            _P._bad("arbitrary_func must be an int32 tensor [B, 1 or Hq, n_func, >= Sq], got "
-                    f"{getattr(func, 'dtype', type(func).__name__)} {tuple(getattr(func, 'shape', ()))}")
-        B, Sq, Hq = q.shape[0], q.shape[1], q.shape[2]
-        if func.shape[0] != B or func.shape[1] not in (1, Hq) or func.shape[2] % 2 != 1 or func.shape[3] < Sq:
-            _P._bad(f"arbitrary_func must be [B={B}, 1 or Hq={Hq}, n_func (odd), >= Sq={Sq}], got shape {tuple(func.shape)}")
-        if func.shape[2] > MAX_N_FUNC:   # refused here, before the forward, rather than at backward time
-            _P._bad(f"arbitrary_func with n_func={func.shape[2]} > {MAX_N_FUNC} is not supported by the backward")
-        mask = MASK_FUNC
-    elif aux_tensors:
-        _P._bad("aux_tensors are given but arbitrary=False")
-    _P._require_gpu(q=q, k=k, v=v, arbitrary_func=func)
+    mask, func = _P._validate_dense(q, k, v, causal, arbitrary, aux_tensors, unsupported, max_n_func=MAX_N_FUNC)
     out, lse = SoftmaxAttn.apply(q, k, v, None, None, 0, 0, mask, func, _P._scale(softmax_scale, q.shape[-1]), skip_tiles)
     return (out, lse) if return_lse else out
 
@@ -128,17 +100,7 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     causal holds inside each sequence, aligned bottom-right.  max_seqlen_q bounds the forward and the dQ launch,
     max_seqlen_k the dK / dV launch: keys of a sequence at or past max_seqlen_k receive no gradient, so it must be at least
     the longest key sequence, as max_seqlen_q must be at least the longest query sequence."""
-    _P._refuse_unsupported(unsupported)
-    _P._validate_qkv(q, k, v, jagged=True)
-    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
-        if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.dtype != torch.int32 or cu.shape[0] < 1:
-            _P._bad(f"{name} must be an int32 tensor [B + 1], got {getattr(cu, 'dtype', type(cu).__name__)} "
-                    f"{tuple(getattr(cu, 'shape', ()))}")
-    if cu_seqlens_q.shape != cu_seqlens_k.shape:
-        _P._bad(f"cu_seqlens_q {tuple(cu_seqlens_q.shape)} and cu_seqlens_k {tuple(cu_seqlens_k.shape)} differ in length")
-    if not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or not isinstance(max_seqlen_k, int) or max_seqlen_k < 0:
-        _P._bad(f"max_seqlen_q / max_seqlen_k must be non-negative ints, got {max_seqlen_q!r}, {max_seqlen_k!r}")
-    _P._require_gpu(q=q, k=k, v=v, cu_seqlens_q=cu_seqlens_q, cu_seqlens_k=cu_seqlens_k)
-    out, lse = SoftmaxAttn.apply(q, k, v, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), max_seqlen_q, max_seqlen_k,
+    cu_q, cu_k = _P._validate_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, unsupported)
+    out, lse = SoftmaxAttn.apply(q, k, v, cu_q, cu_k, max_seqlen_q, max_seqlen_k,
                                  MASK_CAUSAL if causal else MASK_NONE, None, _P._scale(softmax_scale, q.shape[-1]), skip_tiles)
     return (out, lse) if return_lse else out

@@ -273,6 +273,72 @@ def test_validation_and_refusals_are_those_of_prefill_attn():
         S.flash_attn_varlen_func(qj, kj, kj, cu, cu, 5, 5, causal=True)
 
 
+def _bad_calls():
+    """name -> (function name, args, kwargs): calls that both surfaces refuse before any GPU work (all tensors on the CPU)"""
+    BF, I32 = torch.bfloat16, torch.int32
+    q, k = torch.zeros(2, 5, 4, 64, dtype=BF), torch.zeros(2, 7, 2, 64, dtype=BF)
+    fn = lambda *s, dtype=I32: torch.zeros(*s, dtype=dtype)   # noqa: E731
+    qj, kj = torch.zeros(9, 4, 64, dtype=BF), torch.zeros(9, 2, 64, dtype=BF)
+    cu = torch.tensor([0, 4, 9], dtype=I32)
+    D, V = "flash_attn_func", "flash_attn_varlen_func"
+    return {
+        "non-tensor q": (D, ([[1.0]], k, k), {}),
+        "wrong rank": (D, (q[0], k, k), {}),
+        "wrong rank, jagged": (V, (q, k, k, cu, cu, 5, 5), {}),
+        "v shape differs from k": (D, (q, k, torch.zeros(2, 8, 2, 64, dtype=BF)), {}),
+        "Hq no multiple of Hkv": (D, (q, torch.zeros(2, 7, 3, 64, dtype=BF), torch.zeros(2, 7, 3, 64, dtype=BF)), {}),
+        "fp32 q": (D, (q.float(), k, k), {}),
+        "D = 96": (D, (torch.zeros(2, 5, 4, 96, dtype=BF), torch.zeros(2, 7, 2, 96, dtype=BF), torch.zeros(2, 7, 2, 96, dtype=BF)), {}),
+        "stride(-1) != 1": (D, (torch.zeros(2, 5, 4, 128, dtype=BF)[..., ::2], k, k), {}),
+        "causal with arbitrary": (D, (q, k, k), dict(causal=True, arbitrary=True, aux_tensors=[fn(2, 1, 3, 5)])),
+        "no aux tensor": (D, (q, k, k), dict(arbitrary=True)),
+        "zero aux tensors": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[])),
+        "two aux tensors": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 1, 3, 5), fn(2, 1, 3, 5)])),
+        "func not int32": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 1, 3, 5, dtype=torch.int64)])),
+        "func not 4-D": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 3, 5)])),
+        "even n_func": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 1, 4, 5)])),
+        "func too short for Sq": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 1, 3, 4)])),
+        "aux_tensors without arbitrary": (D, (q, k, k), dict(aux_tensors=[fn(2, 1, 3, 5)])),
+        "cu_seqlens not int32": (V, (qj, kj, kj, cu.long(), cu, 5, 5), {}),
+        "unequal cu lengths": (V, (qj, kj, kj, cu, cu[:2], 5, 5), {}),
+        "negative max_seqlen": (V, (qj, kj, kj, cu, cu, 5, -1), {}),
+        "unsupported keyword, dense": (D, (q, k, k), dict(dropout_p=0.1)),
+        "unsupported keyword, jagged": (V, (qj, kj, kj, cu, cu, 5, 5), dict(window_size=(16, 0))),
+        "unknown keyword": (D, (q, k, k), dict(no_such_argument=1)),
+        "unknown keyword, jagged": (V, (qj, kj, kj, cu, cu, 5, 5), dict(no_such_argument=1)),
+        "CPU tensor": (D, (q, k, k), dict(causal=True)),
+        "CPU tensor, func": (D, (q, k, k), dict(arbitrary=True, aux_tensors=[fn(2, 4, 5, 8)])),
+        "CPU tensor, jagged": (V, (qj, kj, kj, cu, cu, 5, 5), dict(causal=True)),
+    }
+
+
+def test_both_surfaces_refuse_a_bad_call_with_the_same_exception_and_message():
+    """prefill_attn and softmax_attn validate through one function (prefill_attn._validate_dense / _validate_varlen); the
+    backward's limit on n_func is the only refusal that softmax_attn adds."""
+    import prefill_attn as P
+    import softmax_attn as S
+
+    for name, (fname, args, kw) in _bad_calls().items():
+        raised = []
+        for mod in (P, S):
+            with pytest.raises(Exception) as ei:
+                getattr(mod, fname)(*args, **kw)
+            raised.append(ei.value)
+        assert type(raised[0]) is type(raised[1]), name
+        assert str(raised[0]) == str(raised[1]) and str(raised[0]), name
+        assert isinstance(raised[0], (P.PrefillAttnError, TypeError)), (name, raised[0])
+    # n_func = 131: the forward-only surface goes on to ask for GPU tensors, the differentiable one refuses the function
+    q, k = torch.zeros(2, 5, 4, 64, dtype=torch.bfloat16), torch.zeros(2, 7, 2, 64, dtype=torch.bfloat16)
+    kw = dict(arbitrary=True, aux_tensors=[torch.zeros(2, 1, 131, 5, dtype=torch.int32)])
+    with pytest.raises(P.PrefillAttnError, match="GPU tensor"):
+        P.flash_attn_func(q, k, k, **kw)
+    with pytest.raises(S.PrefillAttnError, match="n_func=131 > 129 is not supported by the backward"):
+        S.flash_attn_func(q, k, k, **kw)
+    kw = dict(arbitrary=True, aux_tensors=[torch.zeros(2, 1, 129, 5, dtype=torch.int32)])
+    with pytest.raises(S.PrefillAttnError, match="GPU tensor"):   # 129 itself is taken
+        S.flash_attn_func(q, k, k, **kw)
+
+
 def test_the_stand_in_import_names_resolve_to_softmax_attn():
     code = (
         "import sys\n"
